@@ -9,12 +9,20 @@ torch.distributed.run) every rank holds a C2-sized shard (weak scaling) and a st
 radix-partitions both sides and exchanges them with RCCL all-to-all first.
 
 Prints ONE JSON line (rank 0). `value` = probe rows of all ranks / step wall time
-(Mrows/s); `probe_mrows_s` = probe rows / probe-kernel time; `build_ms` = device build
-time. `roofline` prices the probe kernel (the dominant kernel) by its algorithmic bytes
-8P + 16B + 12M over its HIP-event time; `traffic` is the PMC-measured
-HBM bytes per probe launch from profiles/ (null if not measured for this config).
-`cpu_baseline` times the oracle's multithreaded Version-10 restatement (oracle/hj_oracle.c)
-on host cores over a bounded sample (rank 0, N = 1 only).
+(Mrows/s); `ms_per_step` = the wall time of one timed step; `build_ms` = device build
+time. A plain run sets up, warms up, times `--steps` steps and prints the line.
+
+`--full` adds everything that takes runs of its own. `probe_mrows_s` = probe rows /
+probe-kernel time, from instrumented passes after the timed loop. `roofline` prices the
+probe kernel (the dominant kernel) by its algorithmic bytes 8P + 16B + 12M
+over its HIP-event time; `traffic` is the PMC-measured HBM bytes per probe launch from
+profiles/ (null if not measured for this config). `cpu_baseline` times the oracle's
+multithreaded Version-10 restatement (oracle/hj_oracle.c) on host cores (rank 0, N = 1
+only). With N > 1 ranks `--full` also runs the weak-scaling line and checks the pair count
+against the same join without exchange. Without `--full` these fields are null.
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float64):
+the pair count, checksums over all pairs, and a fixed seeded sample of the pairs.
 """
 from __future__ import annotations
 
@@ -40,7 +48,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 # The single-GPU job's timed steps record no timing events: a torch event's system-scope
 # release writes the L2 back between two probes (C2 0.620 -> 0.612 ms per step,
 # profiles/r04_step_events_ab.txt); probe_ms_in_step comes from an instrumented pass after
-# the timed loop. DFP_BENCH_STEP_EVENTS=1: events around every timed probe (rounds 1-3).
+# the timed loop (--full). DFP_BENCH_STEP_EVENTS=1: events around every timed probe (rounds 1-3).
 STEP_EVENTS = os.environ.get("DFP_BENCH_STEP_EVENTS", "0") == "1"
 PERM_MUL = 7368787
 MIX_MUL = 0x9E3779B97F4A7C15  # odd: multiplication mod 2^64 is a bijection of int64
@@ -192,12 +200,23 @@ class SingleGpuJoin:
         self.matches = int(self.d_total.item())
         if self.matches > self.cap:
             raise RuntimeError("output capacity too small")
+        # events around the timed probes (DFP_BENCH_STEP_EVENTS=1) time the probe inside a step
+        self.probe_in_step_ms, self.probe_ms = self.probe_ms, []
+
+    def outputs(self):
+        """The pairs of the last step, as a caller of hj_probe_async receives them."""
+        return self.ob[:self.matches], self.op[:self.matches]
+
+    def measure_probe(self):
+        """--full: the probe's own times, from passes after the timed loop (and after
+        outputs() was read: they write the same pairs again)."""
         if not self.step_events:  # probe_ms_in_step: a few pipelined steps with events, untimed
             build_ms, self.probe_ms, self.step_events = self.build_ms, [], True
             for _ in range(6):
                 self.step()
             self.collect()
             self.build_ms = build_ms
+            self.probe_in_step_ms = self.probe_ms
         # after the timed loop: the probe alone on a finished table (the roofline's
         # launch time; inside the pipeline a probe also waits for the end of its build)
         t = HashTable(1, "int64", self.dev.index or 0)
@@ -218,7 +237,6 @@ class SingleGpuJoin:
         s = self.pstream or torch.cuda.current_stream(self.dev)
         t.stream_wait(s.cuda_stream)
         torch.cuda.synchronize(self.dev)
-        self.probe_in_step_ms = self.probe_ms
         self.probe_ms = []
         for _ in range(5):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -388,10 +406,10 @@ def bench_c4(args, json_out):
     """--config c4: TPC-H Q3 at SF100 (BASELINE.json configs[3], quoted on 8 GPUs; one
     MI355X holds SF100, so this line is the one-GPU plan tpch.q3 with the tables resident in
     HBM). A step = one whole query (filters, both hash joins, the group-by sum, the top 10);
-    value = lineitem rows / s. roofline: the two joins (customer ⋈ orders, orders ⋈
-    lineitem) with 8P + 16B + 12M algorithmic bytes each over their device spans (HIP events
-    around build + probe). cpu_baseline: the same plan on the host at SF1 with the oracle's C
-    join (kind "port")."""
+    value = lineitem rows / s. With --full: roofline: the two joins (customer ⋈ orders,
+    orders ⋈ lineitem) with 8P + 16B + 12M algorithmic bytes each over their device spans (HIP
+    events around build + probe, in runs after the timed ones). cpu_baseline: the same plan on
+    the host at SF1 with the oracle's C join (kind "port")."""
     from datafusion_parallelism_amd import tpch
 
     if int(os.environ.get("WORLD_SIZE", "1")) != 1:
@@ -410,25 +428,38 @@ def bench_c4(args, json_out):
         res = tpch.q3(t, join_fn=tj)
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    # per-join spans from instrumented runs after the timed loop (median of 3)
-    spans = []
-    for _ in range(3):
-        tj.joins, tj.record = [], True
-        tpch.q3(t, join_fn=tj)
-        torch.cuda.synchronize(dev)
-        tj.record = False
-        spans.append([(B, P, M, e0.elapsed_time(e1)) for B, P, M, e0, e1 in tj.joins])
-    joins = []
-    for i in range(len(spans[0])):
-        B, P, M = spans[0][i][:3]
-        ms = float(np.median([s[i][3] for s in spans]))
-        joins.append({"build_rows": B, "probe_rows": P, "matches": M, "ms": round(ms, 4),
-                      "alg_bytes": 8 * P + 16 * B + 12 * M})
-    alg = sum(j["alg_bytes"] for j in joins)
-    jms = sum(j["ms"] for j in joins)
-    achieved = alg / (jms / 1e3) / 1e9
+    if args.dump_outputs:  # the last timed query's rows (at most `limit` of them) and its group count
+        dump_arrays(args.dump_outputs, {
+            "l_orderkey": np.asarray(res.l_orderkey, dtype=np.float64),
+            "revenue": np.asarray(res.revenue, dtype=np.float64),
+            "o_orderdate": np.asarray(res.o_orderdate, dtype=np.float64),
+            "o_shippriority": np.asarray(res.o_shippriority, dtype=np.float64),
+            "groups": np.asarray([res.groups], dtype=np.float64)})
+    joins, roofline, cpu = None, None, None
+    if args.full:
+        # per-join spans from instrumented runs after the timed loop (median of 3)
+        spans = []
+        for _ in range(3):
+            tj.joins, tj.record = [], True
+            tpch.q3(t, join_fn=tj)
+            torch.cuda.synchronize(dev)
+            tj.record = False
+            spans.append([(B, P, M, e0.elapsed_time(e1)) for B, P, M, e0, e1 in tj.joins])
+        joins = []
+        for i in range(len(spans[0])):
+            B, P, M = spans[0][i][:3]
+            ms = float(np.median([s[i][3] for s in spans]))
+            joins.append({"build_rows": B, "probe_rows": P, "matches": M, "ms": round(ms, 4),
+                          "alg_bytes": 8 * P + 16 * B + 12 * M})
+        alg = sum(j["alg_bytes"] for j in joins)
+        jms = sum(j["ms"] for j in joins)
+        achieved = alg / (jms / 1e3) / 1e9
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                    "kernel": "Q3's two hash joins (build + probe each; HIP events around each join)",
+                    "alg_bytes_per_launch": alg, "alg_bytes_formula": "sum over the joins of 8*P + 16*B + 12*M"}
+        cpu = None if args.no_cpu_baseline else cpu_baseline_c4()
     value = nl / (elapsed / args.steps) / 1e6
-    cpu = None if args.no_cpu_baseline else cpu_baseline_c4()
     line = {
         "metric": "probe Mrows/s + build ms, 10^8-row int64 inner join; 1/2/4/8 GPUs",
         "value": round(value, 3), "unit": "Mrows/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -441,10 +472,7 @@ def bench_c4(args, json_out):
         "value_unit_note": "lineitem rows per second of whole queries",
         "query_ms": round(elapsed / args.steps * 1e3, 4),
         "joins": joins,
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                     "kernel": "Q3's two hash joins (build + probe each; HIP events around each join)",
-                     "alg_bytes_per_launch": alg, "alg_bytes_formula": "sum over the joins of 8*P + 16*B + 12*M"},
+        "roofline": roofline,
         "cpu_baseline": cpu,
     }
     print(json.dumps(line), file=json_out, flush=True)
@@ -483,6 +511,36 @@ def load_traffic(config_name):
         with open(p) as f:
             return json.load(f)
     return None
+
+
+DUMP_SAMPLE = 1 << 21  # pairs kept of a larger output: three float64 arrays of 2^21 = 48 MiB
+
+
+def dump_arrays(directory, arrays, suffix=""):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def dump_pairs(directory, b, p, suffix=""):
+    """--dump-outputs: the (build row, probe row) pairs a step emitted (device tensors, in
+    output order) as float64 .npy files. The row ids are below 2^53, so float64 holds them
+    exactly. An output of more than DUMP_SAMPLE pairs is sampled at fixed seeded positions
+    (sorted, the same for every run of the same pair count). `checksums` covers every pair:
+    the pair count, the sums of the build and of the probe ids, and a sum weighted by the
+    output position (mod 2^52), which changes when pairs change places."""
+    n = int(b.numel())
+    if n > DUMP_SAMPLE:
+        pos = torch.from_numpy(np.sort(np.random.default_rng(0xD0).integers(0, n, DUMP_SAMPLE))).to(b.device)
+        sb, sp = b[pos], p[pos]
+    else:
+        pos = torch.arange(n, device=b.device)
+        sb, sp = b, p
+    b64, p64 = b.to(torch.int64), p.to(torch.int64)
+    weight = torch.arange(n, dtype=torch.int64, device=b.device) % 1021 + 1
+    sums = [n, int(b64.sum()), int(p64.sum()), int(((b64 + p64) * weight).sum()) & ((1 << 52) - 1)]
+    dump_arrays(directory, {"build_row_idx": sb.cpu().numpy(), "probe_row_idx": sp.cpu().numpy(),
+                            "sample_positions": pos.cpu().numpy(), "checksums": np.asarray(sums)}, suffix)
 
 
 def _spawn_ranks(n: int) -> int:
@@ -591,7 +649,8 @@ class DryRunJob:
         sk, _ = torch.sort(self.bk)
         t1 = time.perf_counter()
         pos = torch.searchsorted(sk, self.pk).clamp_(max=sk.numel() - 1)
-        self.matches = int((sk[pos] == self.pk).sum())
+        self.hit = sk[pos] == self.pk
+        self.matches = int(self.hit.sum())
         t2 = time.perf_counter()
         self.build_ms.append((t1 - t0) * 1e3)
         self.probe_ms.append((t2 - t1) * 1e3)
@@ -623,6 +682,9 @@ def dry_run(args, json_out):
     if world > 1:
         dist.barrier()
     el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
+    if args.dump_outputs and args.steps > 0:  # the stand-in step's result (the same on every rank)
+        dump_arrays(args.dump_outputs, {"hit": job.hit.numpy(), "matches": np.asarray([job.matches])},
+                    suffix=f"_rank{rank}" if rank else "")
     ranks = torch.tensor([1], dtype=torch.int64)
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -648,7 +710,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS) + ["c4"],
                     help="c2 (the headline), c2h, c3: joins of SURVEY.md §8d; c4: TPC-H Q3 SF100 on one GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything that takes runs of its own: the probe's own times and roofline, the CPU "
+                         "baseline, c4's per-join spans; multi-GPU: the weak-scaling line and the pair-count check "
+                         "against the join without exchange")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64): checksums over all "
+                         "pairs and a fixed seeded sample of them (rank r > 0 writes <name>_rank<r>.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--stream-priority", default="none", choices=["none", "probe-high", "build-low"],
                     help="single GPU: HIP stream priorities of the probe / build streams")
     ap.add_argument("--force-dist", action="store_true",
@@ -775,12 +844,17 @@ def main():
             elapsed = float(t.item())
         return elapsed
 
+    job.keep_outputs = bool(args.dump_outputs)  # the exchange jobs drop a step's pairs otherwise
     elapsed = timed(job, args.steps, args.warmup)
     ms_per_step = elapsed / args.steps * 1e3
     total_probe_rows = gP  # strong scaling: the one global join, whatever the rank count
     value = total_probe_rows / (elapsed / args.steps) / 1e6
+    if args.dump_outputs:  # this rank's pairs of the last timed step
+        dump_pairs(args.dump_outputs, *job.outputs(), suffix=f"_rank{rank}" if rank else "")
+    if args.full and hasattr(job, "measure_probe"):
+        job.measure_probe()
     weak = None
-    if use_dist and world > 1 and not args.no_weak:
+    if args.full and use_dist and world > 1 and not args.no_weak:
         # extra: weak scaling, a config-sized join on every rank (radix all-to-all)
         wbk, wpk, wb0, wp0 = gen_inputs(cfg, rank, world, dev, strong=False)
         wjob = DistJob(dj, wbk, wpk, wb0, wp0, dev)
@@ -791,37 +865,42 @@ def main():
                 "plan": "radix", "exchange_ms": round(float(np.median(wjob.exchange_ms)), 4)}
         del wbk, wpk, wjob
 
-    probe_ms = float(np.median(job.probe_ms))
+    # the probe's own time: the single-GPU job measures it in passes of their own (--full),
+    # the exchange jobs from the timed steps' events
+    probe_ms = float(np.median(job.probe_ms)) if job.probe_ms else None
     build_ms = float(np.median(job.build_ms))
     M = job.matches
     if use_dist:  # pairs of the whole join (all ranks)
-        mt = torch.tensor([M, local_reference_count(cfg, rank, world, dev)], dtype=torch.int64, device=dev)
+        mt = torch.tensor([M, local_reference_count(cfg, rank, world, dev) if args.full else 0], dtype=torch.int64,
+                          device=dev)
         dist.all_reduce(mt)
         M_all, M_ref = int(mt[0].item()), int(mt[1].item())
-        if M_all != M_ref:  # the exchange plan lost or invented pairs
+        if args.full and M_all != M_ref:  # the exchange plan lost or invented pairs
             raise RuntimeError(f"multi-GPU pair count {M_all} != {M_ref} of the same join without exchange")
     else:
         M_all = M
-    alg_bytes = 8 * P + 16 * B + 12 * M
-    achieved = alg_bytes / (probe_ms / 1e3) / 1e9
-    traffic = load_traffic(args.config) if not use_dist else None
-    roofline = {
-        "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBS, 4),
-        "traffic": (traffic or {}).get("hbm_bytes_per_launch"),
-        "traffic_lower": ((traffic or {}).get("probe_phase") or {}).get("hbm_bytes_lower"),
-        "kernel": job.kernel_desc,
-        "alg_bytes_per_launch": alg_bytes,
-        "alg_bytes_formula": "8*P + 16*B + 12*M (SURVEY.md §8d)",
-        # the probe rows' lookups run out of LDS (no random device reads per row); the HBM
-        # streams of the sliced pipeline (keys, entries, refs, rows, pairs) are in DESIGN.md §4
-        "probe_rows_per_s": round(P / (probe_ms / 1e3) / 1e9, 2),
-        "probe_rows_unit": "G/s",
-    }
+    roofline = None
+    if probe_ms is not None:
+        alg_bytes = 8 * P + 16 * B + 12 * M
+        achieved = alg_bytes / (probe_ms / 1e3) / 1e9
+        traffic = load_traffic(args.config) if not use_dist else None
+        roofline = {
+            "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": (traffic or {}).get("hbm_bytes_per_launch"),
+            "traffic_lower": ((traffic or {}).get("probe_phase") or {}).get("hbm_bytes_lower"),
+            "kernel": job.kernel_desc,
+            "alg_bytes_per_launch": alg_bytes,
+            "alg_bytes_formula": "8*P + 16*B + 12*M (SURVEY.md §8d)",
+            # the probe rows' lookups run out of LDS (no random device reads per row); the HBM
+            # streams of the sliced pipeline (keys, entries, refs, rows, pairs) are in DESIGN.md §4
+            "probe_rows_per_s": round(P / (probe_ms / 1e3) / 1e9, 2),
+            "probe_rows_unit": "G/s",
+        }
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(cfg)
         line = {
             "metric": "probe Mrows/s + build ms, 10^8-row int64 inner join; 1/2/4/8 GPUs",
@@ -843,8 +922,8 @@ def main():
                 "matches": M_all,
                 "parallelism": "single-gpu" if not use_dist else f"{plan} x{world} (RCCL)",
             },
-            "probe_mrows_s": round(P / (probe_ms / 1e3) / 1e6, 1),
-            "probe_ms": round(probe_ms, 4),
+            "probe_mrows_s": round(P / (probe_ms / 1e3) / 1e6, 1) if probe_ms is not None else None,
+            "probe_ms": round(probe_ms, 4) if probe_ms is not None else None,
             "probe_ms_in_step": (round(float(np.median(job.probe_in_step_ms)), 4)
                                  if getattr(job, "probe_in_step_ms", None) else None),
             "build_ms": round(build_ms, 4),
@@ -930,9 +1009,11 @@ class DistJob:
         self.collect()
 
     def _collect(self, table, result, ev, native=False):
-        b, _ = result()
+        b, p = result()
         self.matches = int(b.numel())
-        del b, _
+        if getattr(self, "keep_outputs", False):
+            self._last = (b, p)
+        del b, p
         if native:  # hj_dist_join_radix: the job's own stage events (build side, exchange, probe)
             bms, xms, pms = result.job.times()
             self.build_ms.append(bms)
@@ -950,6 +1031,10 @@ class DistJob:
 
     def finish(self):
         self.collect()
+
+    def outputs(self):
+        """The pairs of the last collected step (kept only with keep_outputs set)."""
+        return self._last
 
 
 class ShardedJob:
@@ -1013,8 +1098,10 @@ class ShardedJob:
             self._collect(*pending)
 
     def _collect(self, table, result, ev, native):
-        b, _ = result()
+        b, p = result()
         self.matches = int(b.numel())
+        if getattr(self, "keep_outputs", False):
+            self._last = (b, p)
         ev["end"].synchronize()
         # the build side (plan, exchange, local build, gathers) on the build stream; the
         # probe from its launch to its end on the probe stream (with any wait for the table)
@@ -1037,6 +1124,10 @@ class ShardedJob:
     def finish(self):
         self.drain()
         self.collect()
+
+    def outputs(self):
+        """The pairs of the last collected step (kept only with keep_outputs set)."""
+        return self._last
 
 
 class BroadcastJob:
@@ -1138,6 +1229,9 @@ class BroadcastJob:
         self.matches = int(self.d_total.item())
         if self.matches > self.cap:
             raise RuntimeError("output capacity too small")
+
+    def outputs(self):
+        return self.ob[:self.matches], self.op[:self.matches]
 
 
 if __name__ == "__main__":

@@ -23,7 +23,7 @@ tests)
 bench)
   for cfg in ${CFGS:-c2 c3 c2h}; do
     cb=--no-cpu-baseline; [ "$cfg" = c2 ] && [ -n "$CPUB" ] && cb=
-    step 400 python3 bench.py --config $cfg $cb > $O/bench_$cfg.json 2> $O/bench_$cfg.err
+    step 400 python3 bench.py --full --config $cfg $cb > $O/bench_$cfg.json 2> $O/bench_$cfg.err
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d['probe_ms'], d['roofline']['frac'], d.get('build_ms'))" $O/bench_$cfg.json $cfg
   done ;;
 ks)
@@ -40,7 +40,7 @@ ab)
     for cfg in ${CFGS:-c2}; do
       for r in $RUNS; do
         n=${r%%:*}; ev=${r#*:}
-        env ${ev//,/ } timeout -k 10 300 python3 bench.py --no-cpu-baseline --config $cfg > $O/ab_${cfg}_${n}_$rep.json 2> $O/ab_${cfg}_${n}_$rep.err || { echo "FAILED ab $cfg $n"; exit 1; }
+        env ${ev//,/ } timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --config $cfg > $O/ab_${cfg}_${n}_$rep.json 2> $O/ab_${cfg}_${n}_$rep.err || { echo "FAILED ab $cfg $n"; exit 1; }
         python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d['probe_ms'], d['roofline']['frac'], d.get('build_ms'))" $O/ab_${cfg}_${n}_$rep.json "$cfg $n rep$rep"
       done
     done
