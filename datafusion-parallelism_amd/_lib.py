@@ -23,6 +23,7 @@ HJ_OK, HJ_ERR_INVALID, HJ_ERR_OOM, HJ_ERR_HIP, HJ_ERR_RCCL, HJ_ERR_CAPACITY, HJ_
 HJ_INT32, HJ_INT64 = 0, 1
 HJ_INPUT_DEVICE, HJ_BORROW, HJ_OUTPUT_HOST, HJ_IDS_U31, HJ_BORROW_KEEP = 1, 2, 4, 8, 16
 HJ_MULTI_AUTO, HJ_MULTI_BROADCAST, HJ_MULTI_RADIX = 0, 1, 2
+HJ_FILTER_AUTO, HJ_FILTER_RANGE, HJ_FILTER_BLOOM = 0, 1, 2
 
 STATUS_NAMES = {
     HJ_OK: "HJ_OK", HJ_ERR_INVALID: "HJ_ERR_INVALID", HJ_ERR_OOM: "HJ_ERR_OOM", HJ_ERR_HIP: "HJ_ERR_HIP",
@@ -60,6 +61,12 @@ class HjPartSpec(ctypes.Structure):
 
 class HjDistInfo(ctypes.Structure):
     _fields_ = [("build_rows", ctypes.c_int64), ("recv_rows", ctypes.c_int64), ("sharded", ctypes.c_int)]
+
+
+class HjKeyFilterInfo(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("exact", ctypes.c_int), ("nwords", ctypes.c_uint64),
+                ("key_lo", ctypes.c_int64), ("key_hi", ctypes.c_int64), ("expected_keys", ctypes.c_int64),
+                ("dropped_adds", ctypes.c_int64)]
 
 
 HJ_COMM_ID_BYTES = 128
@@ -112,6 +119,16 @@ SIGNATURES = [
     ("hj_mark_rows", I32, [P, I32, I64, P, I64, P]),
     ("hj_select_workspace_bytes", I64, [I64]),
     ("hj_select_rows", I32, [P, I64, I32, P, P, P, P]),
+    ("hj_key_filter_plan", I32, [I32, I64, I64, I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]),
+    ("hj_key_filter_create", I32, [I32, I32, I64, I64, I64, P, PP]),
+    ("hj_key_filter_add", I32, [P, I32, P, P, I64, I64, P]),
+    ("hj_key_filter_test", I32, [P, I32, P, P, I64, I64, P, P, P]),
+    ("hj_key_filter_select_workspace_bytes", I64, [I64]),
+    ("hj_key_filter_select", I32, [P, I32, P, P, I64, I64, U32, P, P, P, P, P]),
+    ("hj_key_filter_words", I32, [P, PP, ctypes.POINTER(ctypes.c_uint64)]),
+    ("hj_key_filter_export", I32, [P, P, P]),
+    ("hj_key_filter_info_get", I32, [P, ctypes.POINTER(HjKeyFilterInfo)]),
+    ("hj_key_filter_free", None, [P]),
     ("hj_gather_fixed", I32, [P, P, I64, I32, P, I32, I64, P, P, P]),
     ("hj_gather_var_workspace_bytes", I64, [I64]),
     ("hj_gather_var", I32, [P, I32, P, P, I64, P, I32, I64, P, P, I64, P, P, P, P]),

@@ -2409,6 +2409,217 @@ hj_status hj_select_rows(const uint8_t* flags, int64_t n, int want, uint64_t* ou
     return HJ_OK;
 }
 
+// ---- key filter (hj_filter.hip) ----------------------------------------------------
+
+struct hj_key_filter {
+    int device = 0;
+    int kind = HJ_FILTER_BLOOM;
+    uint64_t nwords = 0;
+    int64_t key_lo = 0, key_hi = 0, expected = 0;
+    void* block = nullptr;  // the words, then the dropped-adds counter (8 bytes)
+    size_t bytes = 0;
+    hipEvent_t ev = nullptr;  // end of the latest launch that uses the filter
+    std::mutex mu;            // ev and add_stream
+    hipStream_t add_stream = nullptr;
+    bool added = false;
+
+    unsigned long long* words() const { return static_cast<unsigned long long*>(block); }
+    unsigned long long* dropped() const { return words() + nwords; }
+    FilterView view() const {
+        FilterView v;
+        v.words = words();
+        v.nwords = nwords;
+        v.lo = key_lo;
+        v.span = kind == HJ_FILTER_RANGE ? (uint64_t)key_hi - (uint64_t)key_lo : 0;
+        v.range = kind == HJ_FILTER_RANGE;
+        return v;
+    }
+};
+
+namespace {
+hj_status filter_call_args(const hj_key_filter* f, hj_key_type key_type, const void* keys, int64_t n) {
+    if (f == nullptr) return fail(HJ_ERR_INVALID, "null filter");
+    if (key_type != HJ_INT32 && key_type != HJ_INT64) return fail(HJ_ERR_INVALID, "unknown key type");
+    if (n < 0) return fail(HJ_ERR_INVALID, "negative length");
+    if (n > 0 && keys == nullptr) return fail(HJ_ERR_INVALID, "null keys");
+    return HJ_OK;
+}
+// the filter's free waits for this launch
+hj_status filter_mark(const hj_key_filter* cf, hipStream_t s, bool add) {
+    hj_key_filter* f = const_cast<hj_key_filter*>(cf);
+    std::lock_guard<std::mutex> g(f->mu);
+    HIP_TRY(hipEventRecord(f->ev, s));
+    if (add) {
+        f->add_stream = s;
+        f->added = true;
+    }
+    return HJ_OK;
+}
+}  // namespace
+
+hj_status hj_key_filter_plan(int kind, int64_t key_lo, int64_t key_hi, int64_t expected_keys, int* out_kind,
+                             uint64_t* out_nwords) {
+    if (out_kind == nullptr || out_nwords == nullptr) return fail(HJ_ERR_INVALID, "null out");
+    if (kind != HJ_FILTER_AUTO && kind != HJ_FILTER_RANGE && kind != HJ_FILTER_BLOOM)
+        return fail(HJ_ERR_INVALID, "unknown filter kind");
+    if (expected_keys < 0) return fail(HJ_ERR_INVALID, "negative expected_keys");
+    constexpr uint64_t kMaxWords = 1ull << 32;
+    const bool ordered = key_lo <= key_hi;
+    const uint64_t span = ordered ? (uint64_t)key_hi - (uint64_t)key_lo : 0;  // values - 1: no overflow
+    const uint64_t range_words = (span >> 6) + 1;
+    if (kind == HJ_FILTER_AUTO) {
+        // values <= 64 * max(expected, 1)  <=>  span < 64 * e  <=>  span / 64 < e
+        const uint64_t e = (uint64_t)std::max<int64_t>(expected_keys, 1);
+        kind = (ordered && (span >> 6) < e && range_words < kMaxWords) ? HJ_FILTER_RANGE : HJ_FILTER_BLOOM;
+    }
+    uint64_t nwords;
+    if (kind == HJ_FILTER_RANGE) {
+        if (!ordered) return fail(HJ_ERR_INVALID, "a range filter needs key_lo <= key_hi");
+        nwords = range_words;
+    } else {
+        nwords = std::max<uint64_t>(1, ((uint64_t)expected_keys + 3) / 4);
+    }
+    if (nwords >= kMaxWords) return fail(HJ_ERR_INVALID, "the filter would take 2^32 words or more");
+    *out_kind = kind;
+    *out_nwords = nwords;
+    return HJ_OK;
+}
+
+hj_status hj_key_filter_create(int device, int kind, int64_t key_lo, int64_t key_hi, int64_t expected_keys,
+                               void* stream, hj_key_filter** out) {
+    if (out == nullptr) return fail(HJ_ERR_INVALID, "null out");
+    *out = nullptr;
+    int k = 0;
+    uint64_t nwords = 0;
+    hj_status st = hj_key_filter_plan(kind, key_lo, key_hi, expected_keys, &k, &nwords);
+    if (st != HJ_OK) return st;
+    const int nd = device_count();
+    if (nd == 0) return fail(HJ_ERR_NO_DEVICE, "no GPU visible: the HIP path cannot run (no CPU fallback)");
+    if (device < 0 || device >= nd) return fail(HJ_ERR_INVALID, "bad device");
+    HIP_TRY(hipSetDevice(device));
+    hj_key_filter* f = new hj_key_filter();
+    f->device = device;
+    f->kind = k;
+    f->nwords = nwords;
+    f->key_lo = key_lo;
+    f->key_hi = key_hi;
+    f->expected = expected_keys;
+    f->bytes = (size_t)(nwords + 1) * 8;
+    hipError_t e;
+    f->block = cache_alloc(device, f->bytes, &e);
+    if (f->block == nullptr) {
+        delete f;
+        return fail(HJ_ERR_OOM, std::string("device allocation: ") + hipGetErrorString(e));
+    }
+    if ((e = hipEventCreateWithFlags(&f->ev, hipEventDisableTiming)) != hipSuccess ||
+        (e = hipMemsetAsync(f->block, 0, f->bytes, (hipStream_t)stream)) != hipSuccess ||
+        (e = hipEventRecord(f->ev, (hipStream_t)stream)) != hipSuccess) {
+        if (f->ev) (void)hipEventDestroy(f->ev);
+        (void)hipDeviceSynchronize();
+        cache_free(device, f->block, f->bytes);
+        delete f;
+        return fail(HJ_ERR_HIP, std::string("key filter setup: ") + hipGetErrorString(e));
+    }
+    *out = f;
+    return HJ_OK;
+}
+
+hj_status hj_key_filter_add(hj_key_filter* f, hj_key_type key_type, const void* keys, const uint8_t* validity,
+                            int64_t validity_offset, int64_t n, void* stream) {
+    hj_status st = filter_call_args(f, key_type, keys, n);
+    if (st != HJ_OK) return st;
+    HIP_TRY(hipSetDevice(f->device));
+    if (!is_device_ptr(keys) || !is_device_ptr(validity))
+        return fail(HJ_ERR_INVALID, "hj_key_filter_add takes device pointers");
+    HIP_TRY(launch_filter_add(f->view(), key_type == HJ_INT64 ? 8 : 4, keys, validity, validity_offset, n,
+                              f->dropped(), (hipStream_t)stream));
+    return filter_mark(f, (hipStream_t)stream, true);
+}
+
+hj_status hj_key_filter_test(const hj_key_filter* f, hj_key_type key_type, const void* keys, const uint8_t* validity,
+                             int64_t validity_offset, int64_t n, uint8_t* out_bitmap, int64_t* d_count,
+                             void* stream) {
+    hj_status st = filter_call_args(f, key_type, keys, n);
+    if (st != HJ_OK) return st;
+    if (d_count == nullptr || (n > 0 && out_bitmap == nullptr)) return fail(HJ_ERR_INVALID, "null pointer");
+    if (reinterpret_cast<uintptr_t>(out_bitmap) & 7) return fail(HJ_ERR_INVALID, "out_bitmap must be 8-byte aligned");
+    HIP_TRY(hipSetDevice(f->device));
+    if (!is_device_ptr(keys) || !is_device_ptr(validity) || !is_device_ptr(out_bitmap) || !is_device_ptr(d_count))
+        return fail(HJ_ERR_INVALID, "hj_key_filter_test takes device pointers");
+    HIP_TRY(launch_filter_test(f->view(), key_type == HJ_INT64 ? 8 : 4, keys, validity, validity_offset, n, out_bitmap,
+                               d_count, (hipStream_t)stream));
+    return filter_mark(f, (hipStream_t)stream, false);
+}
+
+int64_t hj_key_filter_select_workspace_bytes(int64_t n) { return filter_select_workspace(n < 0 ? 0 : n); }
+
+hj_status hj_key_filter_select(const hj_key_filter* f, hj_key_type key_type, const void* keys,
+                               const uint8_t* validity, int64_t validity_offset, int64_t n, uint32_t probe_base,
+                               void* out_keys, uint32_t* out_ids, int64_t* d_count, void* workspace, void* stream) {
+    hj_status st = filter_call_args(f, key_type, keys, n);
+    if (st != HJ_OK) return st;
+    if (d_count == nullptr || workspace == nullptr || (n > 0 && (out_keys == nullptr || out_ids == nullptr)))
+        return fail(HJ_ERR_INVALID, "null pointer");
+    if ((uint64_t)probe_base + (uint64_t)n > (1ull << 32)) return fail(HJ_ERR_INVALID, "probe_base + n exceeds 2^32");
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) return fail(HJ_ERR_INVALID, "workspace not 8-byte aligned");
+    HIP_TRY(hipSetDevice(f->device));
+    if (!is_device_ptr(keys) || !is_device_ptr(validity) || !is_device_ptr(out_keys) || !is_device_ptr(out_ids) ||
+        !is_device_ptr(d_count) || !is_device_ptr(workspace))
+        return fail(HJ_ERR_INVALID, "hj_key_filter_select takes device pointers");
+    HIP_TRY(launch_filter_select(f->view(), key_type == HJ_INT64 ? 8 : 4, keys, validity, validity_offset, n,
+                                 probe_base, out_keys, out_ids, d_count, workspace, (hipStream_t)stream));
+    return filter_mark(f, (hipStream_t)stream, false);
+}
+
+hj_status hj_key_filter_words(const hj_key_filter* f, const uint64_t** words, uint64_t* nwords) {
+    if (f == nullptr || words == nullptr || nwords == nullptr) return fail(HJ_ERR_INVALID, "null pointer");
+    *words = reinterpret_cast<const uint64_t*>(f->words());
+    *nwords = f->nwords;
+    return HJ_OK;
+}
+
+hj_status hj_key_filter_export(const hj_key_filter* f, uint64_t* dst, void* stream) {
+    if (f == nullptr || dst == nullptr) return fail(HJ_ERR_INVALID, "null pointer");
+    HIP_TRY(hipSetDevice(f->device));
+    HIP_TRY(hipMemcpyAsync(dst, f->words(), (size_t)f->nwords * 8, hipMemcpyDefault, (hipStream_t)stream));
+    return filter_mark(f, (hipStream_t)stream, false);
+}
+
+hj_status hj_key_filter_info_get(const hj_key_filter* cf, hj_key_filter_info* out) {
+    if (cf == nullptr || out == nullptr) return fail(HJ_ERR_INVALID, "null pointer");
+    hj_key_filter* f = const_cast<hj_key_filter*>(cf);
+    out->kind = f->kind;
+    out->exact = f->kind == HJ_FILTER_RANGE;
+    out->nwords = f->nwords;
+    out->key_lo = f->key_lo;
+    out->key_hi = f->key_hi;
+    out->expected_keys = f->expected;
+    out->dropped_adds = 0;
+    hipStream_t s;
+    {
+        std::lock_guard<std::mutex> g(f->mu);
+        if (!f->added) return HJ_OK;  // the counter is still the zero of creation
+        s = f->add_stream;
+    }
+    HIP_TRY(hipSetDevice(f->device));
+    unsigned long long d = 0;
+    HIP_TRY(hipMemcpyAsync(&d, f->dropped(), 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->dropped_adds = (int64_t)d;
+    return HJ_OK;
+}
+
+void hj_key_filter_free(hj_key_filter* f) {
+    if (f == nullptr) return;
+    (void)hipSetDevice(f->device);
+    if (f->ev) {
+        (void)hipEventSynchronize(f->ev);
+        (void)hipEventDestroy(f->ev);
+    }
+    cache_free(f->device, f->block, f->bytes);
+    delete f;
+}
+
 hj_status hj_gather_fixed(const void* src, const uint8_t* src_valid, int64_t src_voff, int elem_bytes, const void* idx,
                           int idx_bytes, int64_t n, void* dst, uint8_t* dst_valid, void* stream) {
     if (device_count() == 0) return fail(HJ_ERR_NO_DEVICE, "no GPU visible");

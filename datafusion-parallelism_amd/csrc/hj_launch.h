@@ -152,6 +152,30 @@ hipError_t launch_gather_var(const void* offsets, int offset_bytes, const uint8_
                              uint8_t* out_values, int64_t values_cap, uint8_t* dst_valid, int64_t* d_values_len,
                              void* workspace, hipStream_t s);
 
+// ---- key filter (hj_filter.hip) ----------------------------------------------
+// The filter's words as the kernels see them. range: bit (k - lo) & 63 of word
+// (k - lo) >> 6 for (uint64)(k - lo) <= span (span = key_hi - key_lo, so a full 2^64 range
+// needs no 65th bit); else the one-word blocked Bloom layout of include/hj.h.
+struct FilterView {
+    unsigned long long* words;
+    uint64_t nwords;
+    int64_t lo;
+    uint64_t span;
+    bool range;
+};
+// sets the bits of the valid keys; *dropped += valid keys outside a range filter
+hipError_t launch_filter_add(const FilterView& f, int key_bytes, const void* keys, const uint8_t* valid, int64_t voff,
+                             int64_t n, unsigned long long* dropped, hipStream_t s);
+// out_bitmap: ceil(n / 64) u64 words, bit i = row i valid and present; *d_count = set bits
+hipError_t launch_filter_test(const FilterView& f, int key_bytes, const void* keys, const uint8_t* valid, int64_t voff,
+                              int64_t n, uint8_t* out_bitmap, int64_t* d_count, hipStream_t s);
+// the passing rows' keys (key_bytes each) and ids probe_base + row in row order (capacity
+// n), *d_count their number; workspace: filter_select_workspace(n)
+int64_t filter_select_workspace(int64_t n);
+hipError_t launch_filter_select(const FilterView& f, int key_bytes, const void* keys, const uint8_t* valid,
+                                int64_t voff, int64_t n, uint32_t probe_base, void* out_keys, uint32_t* out_ids,
+                                int64_t* d_count, void* workspace, hipStream_t s);
+
 // ---- multi-GPU table helpers (hj_columns.hip) -------------------------------
 hipError_t launch_iota_u32(uint32_t* out, int64_t n, uint32_t base, hipStream_t s);
 hipError_t launch_add_u32(uint32_t* a, int64_t n, uint32_t base, hipStream_t s);

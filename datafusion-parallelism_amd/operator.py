@@ -52,6 +52,7 @@ import torch
 
 from ._lib import HjError, HJ_ERR_INVALID
 from .columns import DeviceColumn, DeviceRecordBatch, composite_keys, filter_equal_pairs, mark_rows, select_rows
+from .key_filter import KeyFilter
 from .table import HashTable
 
 
@@ -175,7 +176,11 @@ class GpuIndexLookup:
                     torch.empty(0, dtype=torch.int32, device=self.device))
         keys = probe_keys if isinstance(probe_keys, DeviceColumn) else DeviceColumn.from_arrow(probe_keys, self.device)
         # the device validity bitmap goes to the probe as is, from bit voff (no host read)
-        return self.table.probe(keys.key_tensor(), keys.valid, device_output=True, valid_offset=keys.voff)
+        return self.table.probe(keys.key_tensor(), keys.valid, device_output=True, valid_offset=keys.voff,
+                                prefilter=self._prefilter())
+
+    def _prefilter(self) -> "KeyFilter | None":
+        return self._shared.key_filter() if self._shared is not None else None
 
     def _composite_matches(self, arrays: list[pa.Array], build_side_records: pa.RecordBatch | None):
         sh = self._shared
@@ -187,7 +192,7 @@ class GpuIndexLookup:
             return (torch.empty(0, dtype=torch.int64, device=self.device),
                     torch.empty(0, dtype=torch.int32, device=self.device))
         keys, valid = composite_keys(pcols)
-        b, p = self.table.probe(keys, valid, device_output=True)
+        b, p = self.table.probe(keys, valid, device_output=True, prefilter=self._prefilter())
         rb = build_side_records if build_side_records is not None else sh.concatenated()
         bcols = self.build_columns(rb)
         kidx = [e if isinstance(e, int) else rb.schema.get_field_index(e) for e in sh.key_exprs]
@@ -209,8 +214,11 @@ class GpuIndexLookup:
 class _SharedBuild:
     """State shared by all partitions of one build (JoinStateInstances)."""
 
-    def __init__(self, parallelism: int, device: int, devices: Sequence[int] | None = None, plan: str = "auto"):
+    def __init__(self, parallelism: int, device: int, devices: Sequence[int] | None = None, plan: str = "auto",
+                 prefilter: bool = False):
         self.parallelism = parallelism
+        self.prefilter = prefilter      # probes go through a key filter over the build keys
+        self._filter: KeyFilter | None = None
         self.device = devices[0] if devices else device
         self.devices = list(devices) if devices else None
         self.plan = plan
@@ -263,6 +271,27 @@ class _SharedBuild:
                     self.record_batch = DeviceRecordBatch(schema, empty, 0)
             return self.record_batch
 
+    def key_filter(self) -> "KeyFilter | None":
+        """With prefilter on: one filter for all partitions, built by the first probe from
+        the concatenated build batch's key column (the composite int64 keys of several /
+        non-integer key columns: hashes, so the automatic kind is a Bloom filter)."""
+        if not self.prefilter:
+            return None
+        rb = self.concatenated()  # takes the lock itself
+        with self.lock:
+            if self._filter is None:
+                kcols = [rb.device_columns[e if isinstance(e, int) else rb.schema.get_field_index(e)]
+                         for e in self.key_exprs]
+                if rb.num_rows == 0:
+                    self._filter = KeyFilter(self.device)  # an empty build: rejects every row
+                elif self.composite:
+                    keys, valid = composite_keys(kcols)
+                    self._filter = KeyFilter.from_keys(keys, valid)
+                else:
+                    k = kcols[0]
+                    self._filter = KeyFilter.from_keys(k.key_tensor(), k.valid, valid_offset=k.voff)
+            return self._filter
+
     def device_columns(self, rb: pa.RecordBatch, device) -> list[DeviceColumn]:
         """A host build batch's columns in HBM, uploaded once for all partitions (callers
         that pass their own RecordBatch instead of the resident one)."""
@@ -277,8 +306,11 @@ class BuildImplementation:
 
     def __init__(self, build_implementation_version: JoinReplacement, parallelism: int,
                  input_schema: pa.Schema | None = None, device: int = 0, devices: Sequence[int] | None = None,
-                 plan: str = "auto"):
-        """devices: build one table over these GPUs of the node (hj_build_begin_multi;
+                 plan: str = "auto", prefilter: bool = False):
+        """prefilter: every probe first drops the rows a key filter over the build keys
+        rejects (KeyFilter; same output for every join type: the filter only removes rows
+        that have no pair).
+        devices: build one table over these GPUs of the node (hj_build_begin_multi;
         DataFusion runs every partition in one process, so the in-process multi-GPU table
         is the drop-in's node-wide form); plan "auto" | "broadcast" | "radix" (the build
         side sharded by key hash, 1/G per GPU: builds larger than one GPU). Batches and
@@ -290,7 +322,7 @@ class BuildImplementation:
         if devices is not None and len(devices) < 1:
             raise HjError(HJ_ERR_INVALID, "devices must name at least one GPU")
         self.parallelism = parallelism
-        self._shared = _SharedBuild(parallelism, device, devices, plan)
+        self._shared = _SharedBuild(parallelism, device, devices, plan, prefilter)
         self._shared.schema = input_schema
 
     def build_side(self, partition: int, stream: Iterable[pa.RecordBatch], build_expressions: Sequence[str | int],
@@ -485,8 +517,10 @@ class ParallelHashJoin:
     def __init__(self, left: list[list[pa.RecordBatch]], right: list[list[pa.RecordBatch]],
                  on: Sequence[tuple[str, str]], join_type: JoinType | str = JoinType.Inner, device: int = 0,
                  replacement: JoinReplacement = JoinReplacement.Gpu, filter: JoinFilter | None = None,
-                 right_schema: pa.Schema | None = None, devices: Sequence[int] | None = None, plan: str = "auto"):
-        """devices / plan: one build table over several GPUs (BuildImplementation)."""
+                 right_schema: pa.Schema | None = None, devices: Sequence[int] | None = None, plan: str = "auto",
+                 prefilter: bool = False):
+        """devices / plan: one build table over several GPUs (BuildImplementation);
+        prefilter: probe through a key filter over the build keys (BuildImplementation)."""
         if len(on) < 1:
             raise HjError(HJ_ERR_INVALID, "an equi-join needs at least one (left, right) key pair")
         self.join_type = JoinType.parse(join_type)
@@ -497,7 +531,8 @@ class ParallelHashJoin:
         self.on = list(on)
         self.filter = filter
         self.right_schema = right_schema or next((b.schema for part in self.right for b in part), None)
-        self._build = BuildImplementation(replacement, n, device=device, devices=devices, plan=plan)
+        self._build = BuildImplementation(replacement, n, device=device, devices=devices, plan=plan,
+                                          prefilter=prefilter)
         self._finalizer = _Finalizer(n)
 
     def execute(self, partition: int) -> list[pa.RecordBatch]:

@@ -256,13 +256,18 @@ class HashTable:
         return out[:nrows]
 
     # -- probe --------------------------------------------------------------
-    def probe(self, keys, valid=None, device_output: bool = False, valid_offset: int = 0):
+    def probe(self, keys, valid=None, device_output: bool = False, valid_offset: int = 0, prefilter=None):
         """Synchronous probe; returns (build_idx uint64, probe_idx uint32) in canonical
         order as numpy arrays, or as torch device tensors (int64, int32) with
         device_output=True (then keys must be a device tensor; a device bitmap `valid`
-        with `valid_offset` is read in place)."""
+        with `valid_offset` is read in place). prefilter (device output only): a KeyFilter
+        filled from this table's build keys; the rows it rejects are dropped before the
+        probe (hj_key_filter_select -> hj_probe_async_ids) and the pairs stay the same, in
+        the same order."""
         if device_output:
-            return self._probe_device(keys, valid, valid_offset)
+            return self._probe_device(keys, valid, valid_offset, prefilter)
+        if prefilter is not None:
+            raise TypeError("prefilter needs device_output=True (the filter runs on device columns)")
         ki = as_key_input(keys, valid, valid_offset)
         if ki.n and ki.key_type != self.key_type:
             raise TypeError("probe key type differs from the build key type")
@@ -278,13 +283,24 @@ class HashTable:
         finally:
             self._L.hj_pairs_free(ctypes.byref(pr))
 
-    def _probe_device(self, keys: torch.Tensor, valid=None, valid_offset: int = 0):
+    def _probe_device(self, keys: torch.Tensor, valid=None, valid_offset: int = 0, prefilter=None):
         if not (isinstance(keys, torch.Tensor) and keys.is_cuda):
             raise TypeError("device_output=True takes a device tensor of keys")
         ki = as_key_input(keys, valid, valid_offset)
         if ki.n and ki.key_type != self.key_type:
             raise TypeError("probe key type differs from the build key type")
         dev = keys.device
+        ids_ptr = None
+        if prefilter is not None:
+            # the passing rows, compacted in row order with their row numbers as ids: the
+            # workspace and the first output capacity follow the passing count
+            if prefilter.device != (dev.index or 0):
+                raise ValueError("the prefilter lives on another device than the probe keys")
+            fkeys, fids = prefilter.select(keys, valid, valid_offset)
+            if fkeys.numel() == 0:
+                return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev))
+            ki = KeyInput(fkeys.data_ptr(), None, 0, fkeys.numel(), ki.flags, ki.key_type, (fkeys, fids))
+            ids_ptr = fids.data_ptr()
         ws = torch.empty(self.workspace_bytes(ki.n), dtype=torch.uint8, device=dev)
         d_total = torch.zeros(1, dtype=torch.int64, device=dev)
         cap = max(ki.n, 1)
@@ -293,7 +309,7 @@ class HashTable:
             ob = torch.empty(cap, dtype=torch.int64, device=dev)
             op = torch.empty(cap, dtype=torch.int32, device=dev)
             self.probe_async(ki.ptr, ki.n, ob.data_ptr(), op.data_ptr(), cap, d_total.data_ptr(), ws.data_ptr(),
-                             stream, ki.valid_ptr, ki.voff)
+                             stream, ki.valid_ptr, ki.voff, probe_ids_ptr=ids_ptr)
             total = int(d_total.item())
             if int(ws[8:16].view(torch.int64).item()) != 0:
                 raise _lib.HjError(_lib.HJ_ERR_HIP, "probe look-back timed out")

@@ -55,10 +55,12 @@ the hash-join kernels; (partkey, suppkey) is one int64 key partkey << 32 | suppk
 from __future__ import annotations
 
 import datetime as _dt
+import os
 from dataclasses import dataclass
 
 import torch
 
+from .key_filter import KeyFilter
 from .table import HashTable
 
 SEGMENTS = ["AUTOMOBILE", "BUILDING", "FURNITURE", "HOUSEHOLD", "MACHINERY"]
@@ -271,11 +273,18 @@ def year_of(days: torch.Tensor) -> torch.Tensor:
 
 
 def _join(build: torch.Tensor, probe: torch.Tensor):
-    """Inner-join pairs (build row int64, probe row int64) on the GPU hash join."""
+    """Inner-join pairs (build row int64, probe row int64) on the GPU hash join.
+    DFP_TPCH_PREFILTER=1 (read at each call): a key filter over the build keys drops the
+    probe rows that cannot match before the probe (KeyFilter.from_keys); same pairs."""
     dev = probe.device
+    build = build.contiguous()
     with HashTable(1, "int64", dev.index or 0) as t:
-        t.build(build.contiguous())
-        b, p = t.probe(probe.contiguous(), device_output=True)
+        t.build(build)
+        if os.environ.get("DFP_TPCH_PREFILTER") == "1":
+            with KeyFilter.from_keys(build) as f:
+                b, p = t.probe(probe.contiguous(), device_output=True, prefilter=f)
+        else:
+            b, p = t.probe(probe.contiguous(), device_output=True)
     return b, p.to(torch.int64)
 
 

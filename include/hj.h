@@ -440,6 +440,113 @@ hj_status hj_gather_var(const void* offsets, int offset_bytes, const uint8_t* va
                         int64_t n, void* out_offsets, uint8_t* out_values, int64_t values_cap,
                         uint8_t* dst_valid, int64_t* d_values_len, void* workspace, void* stream);
 
+/* ---- key filter: drops probe rows that cannot match before they read the table.
+ *      New (no reference counterpart: the reference probes every row,
+ *      lookup_implementation_3.rs:22-59). Flow: hj_key_minmax over the build keys ->
+ *      hj_key_filter_create -> hj_key_filter_add per build batch -> hj_key_filter_select
+ *      per probe batch -> hj_probe_async_ids on the compacted (keys, ids): the pairs are
+ *      those of a probe of the whole batch, in the same order. Opt-in: nothing else in
+ *      the library uses a filter by itself. Device pointers, asynchronous on `stream`, no
+ *      host synchronisation except where stated.
+ *
+ * A filter is an array of `nwords` uint64 words in device memory, zeroed at creation, of
+ * one of two kinds. Keys are compared after widening to int64: an int32 and an int64
+ * column of equal values fill and hit the same bits, and every call names the hj_key_type
+ * of its own column. Null keys are never added and never pass.
+ *
+ *   HJ_FILTER_RANGE (exact, no false positives): a bitmap over [key_lo, key_hi].
+ *     nwords = ceil((key_hi - key_lo + 1) / 64). With d = (uint64)k - (uint64)key_lo
+ *     (unsigned 64-bit wrap-around subtraction), key k is present iff
+ *     d < key_hi - key_lo + 1 and bit (d & 63) of word (d >> 6) is set.
+ *   HJ_FILTER_BLOOM (one-word blocked Bloom filter, 16 bits per expected key):
+ *     nwords = max(1, ceil(expected_keys / 4)). With h = mix64((uint64)k),
+ *       mix64(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33;
+ *                 x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33   (mod 2^64; murmur3's fmix64),
+ *     the word is ((h >> 32) * nwords) >> 32 and the mask is the OR over j = 0..3 of
+ *     1 << ((h >> 6j) & 63); key k is present iff (word & mask) == mask.
+ *   Both kinds: nwords must be below 2^32.
+ *   HJ_FILTER_AUTO: RANGE when key_lo <= key_hi and the range spans at most
+ *     64 * max(expected_keys, 1) values (at most 8 bytes of filter per key) in fewer than
+ *     2^32 words; else BLOOM. key_lo > key_hi (hj_key_minmax of an empty build) gives a
+ *     BLOOM filter that stays zero and rejects every row (one word for expected_keys 0). */
+enum { HJ_FILTER_AUTO = 0, HJ_FILTER_RANGE = 1, HJ_FILTER_BLOOM = 2 };
+
+typedef struct hj_key_filter hj_key_filter; /* opaque, device resident */
+
+typedef struct hj_key_filter_info {
+    int kind;              /* HJ_FILTER_RANGE or HJ_FILTER_BLOOM (AUTO resolved) */
+    int exact;             /* 1: no false positives (RANGE) */
+    uint64_t nwords;
+    int64_t key_lo;        /* as given to hj_key_filter_create */
+    int64_t key_hi;
+    int64_t expected_keys;
+    int64_t dropped_adds;  /* valid keys outside [key_lo, key_hi] that hj_key_filter_add ignored (RANGE) */
+} hj_key_filter_info;
+
+/* The kind (AUTO resolved) and word count hj_key_filter_create would choose; needs no GPU.
+ * HJ_ERR_INVALID for a bad kind, a negative expected_keys, RANGE with key_lo > key_hi, or
+ * a word count of 2^32 or more. New (no reference counterpart: the reference probes every
+ * row, lookup_implementation_3.rs:22-59). */
+hj_status hj_key_filter_plan(int kind, int64_t key_lo, int64_t key_hi, int64_t expected_keys, int* out_kind,
+                             uint64_t* out_nwords);
+
+/* A zeroed filter on GPU `device` (its memory comes from the library's device block cache
+ * and is zeroed on `stream`). HJ_ERR_INVALID as hj_key_filter_plan; HJ_ERR_OOM when the
+ * allocation fails. New (no reference counterpart: the reference probes every row,
+ * lookup_implementation_3.rs:22-59). */
+hj_status hj_key_filter_create(int device, int kind, int64_t key_lo, int64_t key_hi, int64_t expected_keys,
+                               void* stream, hj_key_filter** out);
+
+/* Sets the bits of the valid keys of one batch (validity: Arrow LSB bitmap from bit
+ * validity_offset, NULL = all valid). Any number of calls, from any partitions' batches:
+ * the words do not depend on the order (OR is commutative). A RANGE filter ignores keys
+ * outside [key_lo, key_hi] and counts them (hj_key_filter_info.dropped_adds): a probe key
+ * equal to such a build key is then rejected, so take the range from the build keys
+ * themselves. New (no reference counterpart: the reference probes every row,
+ * lookup_implementation_3.rs:22-59). */
+hj_status hj_key_filter_add(hj_key_filter* f, hj_key_type key_type, const void* keys, const uint8_t* validity,
+                            int64_t validity_offset, int64_t n, void* stream);
+
+/* out_bitmap (Arrow LSB bitmap, 8-byte aligned, ceil(n / 64) * 8 bytes): bit i = row i is
+ * valid and present; *d_count (device int64) = the number of set bits. The bitmap can be
+ * handed to any hj_probe* as its `validity` (offset 0). New (no reference counterpart: the
+ * reference probes every row, lookup_implementation_3.rs:22-59). */
+hj_status hj_key_filter_test(const hj_key_filter* f, hj_key_type key_type, const void* keys,
+                             const uint8_t* validity, int64_t validity_offset, int64_t n, uint8_t* out_bitmap,
+                             int64_t* d_count, void* stream);
+
+/* The valid and present rows' keys (out_keys, in key_type) and their ids probe_base + row
+ * (out_ids), in ascending row order, into buffers of capacity n; *d_count (device int64)
+ * their number. probe_base + n must not exceed 2^32. The output feeds hj_probe_async_ids
+ * directly (no validity: every row written is valid). workspace (device, 8-byte aligned):
+ * hj_key_filter_select_workspace_bytes(n) bytes, not shared by concurrent calls. New (no
+ * reference counterpart: the reference probes every row, lookup_implementation_3.rs:22-59). */
+int64_t hj_key_filter_select_workspace_bytes(int64_t n);
+hj_status hj_key_filter_select(const hj_key_filter* f, hj_key_type key_type, const void* keys,
+                               const uint8_t* validity, int64_t validity_offset, int64_t n, uint32_t probe_base,
+                               void* out_keys, uint32_t* out_ids, int64_t* d_count, void* workspace, void* stream);
+
+/* The filter's words (device pointer, valid until hj_key_filter_free) and their number,
+ * for export to another device or host and for tests; complete once the adds' streams
+ * have run. New (no reference counterpart: the reference probes every row,
+ * lookup_implementation_3.rs:22-59). */
+hj_status hj_key_filter_words(const hj_key_filter* f, const uint64_t** words, uint64_t* nwords);
+
+/* Copies the words to dst (nwords uint64; device memory, or host memory the caller
+ * synchronises `stream` to read) on `stream`, after the adds enqueued on it. New (no
+ * reference counterpart: the reference probes every row, lookup_implementation_3.rs:22-59). */
+hj_status hj_key_filter_export(const hj_key_filter* f, uint64_t* dst, void* stream);
+
+/* Synchronises the stream of the last hj_key_filter_add to read dropped_adds. New (no
+ * reference counterpart: the reference probes every row, lookup_implementation_3.rs:22-59). */
+hj_status hj_key_filter_info_get(const hj_key_filter* f, hj_key_filter_info* out);
+
+/* Waits for the filter's latest launch, then releases its memory (work still running on
+ * other streams must be finished by the caller first, as for hj_table_free). NULL is a
+ * no-op. New (no reference counterpart: the reference probes every row,
+ * lookup_implementation_3.rs:22-59). */
+void hj_key_filter_free(hj_key_filter* f);
+
 /* ---- join keys of several columns, or of non-integer types (SURVEY.md §8a a2/a12:
  *      calculate_hash over every key column, src/shared/shared.rs:11-16, and the
  *      equality re-check equal_rows_arr, src/shared/datafusion_private.rs:52-73). ------
