@@ -108,6 +108,8 @@ SIGNATURES = [
     ("hj_probe_async", I32, [P, P, P, I64, I64, P, P, I64, P, P, P]),
     ("hj_probe_async_ids", I32, [P, P, P, I64, P, I64, P, P, I64, P, P, P]),
     ("hj_probe_async_base", I32, [P, P, P, I64, I64, U32, P, P, I64, P, P, P]),
+    ("hj_probe_match_workspace_bytes", I64, [P, I64]),
+    ("hj_probe_match", I32, [P, P, P, I64, I64, P, P, P, I64, P, P, P]),
     ("hj_table_stream_wait", I32, [P, P]),
     ("hj_partition_workspace_bytes", I64, [I64, I32]),
     ("hj_radix_partition", I32, [I32, P, P, I64, P, U64, I64, I32, P, I32, I64, P, I32, P, P, P]),
@@ -119,6 +121,8 @@ SIGNATURES = [
     ("hj_mark_rows", I32, [P, I32, I64, P, I64, P]),
     ("hj_select_workspace_bytes", I64, [I64]),
     ("hj_select_rows", I32, [P, I64, I32, P, P, P, P]),
+    ("hj_select_bitmap_workspace_bytes", I64, [I64]),
+    ("hj_select_bitmap", I32, [P, I64, I64, I32, U32, P, P, P, P]),
     ("hj_key_filter_plan", I32, [I32, I64, I64, I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]),
     ("hj_key_filter_create", I32, [I32, I32, I64, I64, I64, P, PP]),
     ("hj_key_filter_add", I32, [P, I32, P, P, I64, I64, P]),

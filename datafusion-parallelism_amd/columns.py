@@ -298,6 +298,24 @@ def select_rows(flags: torch.Tensor, want: int, n: int | None = None) -> torch.T
     return out[: int(cnt.item())]
 
 
+def select_bitmap(bitmap: torch.Tensor, n: int, want: int, base: int = 0, bit_offset: int = 0) -> torch.Tensor:
+    """Ascending base + i, i < n, whose bit bit_offset + i of the Arrow LSB bitmap (uint8
+    device tensor, e.g. HashTable.probe_match's) equals want (0 or 1): hj_select_bitmap,
+    an int32 device tensor (the bits of uint32 rows, as the probe's probe_idx)."""
+    L = _lib.load()
+    dev = bitmap.device
+    if bitmap.dtype != torch.uint8 or not bitmap.is_contiguous():
+        raise TypeError("bitmap must be a contiguous uint8 tensor")
+    if (bit_offset + n + 7) // 8 > bitmap.numel():
+        raise ValueError("bitmap is shorter than bit_offset + n bits")
+    out = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = torch.empty(L.hj_select_bitmap_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    check(L.hj_select_bitmap(bitmap.data_ptr() if n else None, bit_offset, n, want, base, out.data_ptr(),
+                             cnt.data_ptr(), ws.data_ptr(), _stream(dev)))
+    return out[: int(cnt.item())]
+
+
 class DeviceRecordBatch:
     """The concatenated build RecordBatch, resident in HBM (row i <-> build index i): what
     the reference hands every partition's consumer with the lookup

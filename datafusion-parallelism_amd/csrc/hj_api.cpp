@@ -1981,6 +1981,49 @@ hj_status hj_probe_async_ids(const hj_table* t, const void* keys, const uint8_t*
                       workspace, (hipStream_t)stream /* NULL = the null stream */);
 }
 
+// ---- match probe --------------------------------------------------------------------
+
+namespace {
+// bits of the per-call claim bitmap of a settled single-device table (launch_probe_match):
+// one per key value of a direct-addressed table (a wrapped one's segment array has no
+// length here, its key range does), else one per 8 words of the duplicate-segment array
+uint64_t match_claim_bits(const hj_table* t) {
+    return t->dense != nullptr ? t->drange : ((uint64_t)(2 * t->total_rows + 2) >> 3) + 1;
+}
+const char* const kMatchMulti = "the match probe is not defined for a multi-GPU table (probe its pairs instead)";
+}  // namespace
+
+int64_t hj_probe_match_workspace_bytes(const hj_table* t, int64_t n) {
+    if (check_table(t) != HJ_OK) return -1;  // settles a pending layout: the size depends on it
+    if (t->multi) {
+        (void)fail(HJ_ERR_INVALID, kMatchMulti);
+        return -1;
+    }
+    if (check_probe_args(n, 0, 0, nullptr) != HJ_OK) return -1;
+    return probe_match_workspace(match_claim_bits(t));
+}
+
+hj_status hj_probe_match(const hj_table* t, const void* keys, const uint8_t* validity, int64_t validity_offset,
+                         int64_t n, uint8_t* out_bitmap, uint32_t* out_counts, uint8_t* build_flags, int64_t nflags,
+                         int64_t* d_stats, void* workspace, void* stream) {
+    hj_status st = check_table(t);
+    if (st != HJ_OK) return st;
+    if (t->multi) return fail(HJ_ERR_INVALID, kMatchMulti);
+    if (workspace == nullptr) return fail(HJ_ERR_INVALID, "null workspace");
+    if ((st = check_probe_args(n, 0, 0, workspace)) != HJ_OK) return st;
+    if (n > 0 && keys == nullptr) return fail(HJ_ERR_INVALID, "null keys");
+    if (nflags < 0 || (nflags > 0 && build_flags == nullptr)) return fail(HJ_ERR_INVALID, "bad build_flags / nflags");
+    if (reinterpret_cast<uintptr_t>(out_bitmap) & 7) return fail(HJ_ERR_INVALID, "out_bitmap must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(out_counts) & 3) || (reinterpret_cast<uintptr_t>(d_stats) & 7))
+        return fail(HJ_ERR_INVALID, "out_counts must be 4-byte and d_stats 8-byte aligned");
+    HIP_TRY(hipSetDevice(t->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((st = wait_built(t, s)) != HJ_OK) return st;  // the probe orders itself after the build
+    HIP_TRY(launch_probe_match(t->key_bytes, view_of(t), keys, validity, validity_offset, n, out_bitmap, out_counts,
+                               build_flags, nflags, d_stats, workspace, match_claim_bits(t), s));
+    return note_probe(t, s);  // hj_table_free waits for it
+}
+
 hj_status hj_probe(const hj_table* t, const void* keys, const uint8_t* validity, int64_t validity_offset, int64_t n,
                    uint32_t flags, void* stream, hj_pairs* out) {
     hj_status st = check_table(t);
@@ -2406,6 +2449,24 @@ hj_status hj_select_rows(const uint8_t* flags, int64_t n, int want, uint64_t* ou
     if (!is_device_ptr(flags) || !is_device_ptr(out) || !is_device_ptr(d_count) || !is_device_ptr(workspace))
         return fail(HJ_ERR_INVALID, "hj_select_rows takes device pointers");
     HIP_TRY(launch_select_rows(flags, n, (uint8_t)want, out, d_count, workspace, (hipStream_t)stream));
+    return HJ_OK;
+}
+
+int64_t hj_select_bitmap_workspace_bytes(int64_t n) { return select_bitmap_workspace(n < 0 ? 0 : n); }
+
+hj_status hj_select_bitmap(const uint8_t* bitmap, int64_t bit_offset, int64_t n, int want, uint32_t base,
+                           uint32_t* out_rows, int64_t* d_count, void* workspace, void* stream) {
+    if (n < 0 || bit_offset < 0 || (want != 0 && want != 1)) return fail(HJ_ERR_INVALID, "bad arguments");
+    if ((int64_t)base + n > 0x100000000ll) return fail(HJ_ERR_INVALID, "base + rows exceeds 2^32");
+    if (d_count == nullptr || workspace == nullptr || (n > 0 && (bitmap == nullptr || out_rows == nullptr)))
+        return fail(HJ_ERR_INVALID, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 7) || (reinterpret_cast<uintptr_t>(d_count) & 7) ||
+        (reinterpret_cast<uintptr_t>(out_rows) & 3))
+        return fail(HJ_ERR_INVALID, "workspace and d_count must be 8-byte, out_rows 4-byte aligned");
+    if (device_count() == 0) return fail(HJ_ERR_NO_DEVICE, "no GPU visible");
+    if (!is_device_ptr(bitmap) || !is_device_ptr(out_rows) || !is_device_ptr(d_count) || !is_device_ptr(workspace))
+        return fail(HJ_ERR_INVALID, "hj_select_bitmap takes device pointers");
+    HIP_TRY(launch_select_bitmap(bitmap, bit_offset, n, want, base, out_rows, d_count, workspace, (hipStream_t)stream));
     return HJ_OK;
 }
 

@@ -116,6 +116,85 @@ hipError_t launch_select_rows(const uint8_t* flags, int64_t n, uint8_t want, uin
 }
 
 // ---------------------------------------------------------------------------
+// stream compaction of bitmap positions (ascending): get_semi_indices / get_anti_indices
+// (src/shared/datafusion_private.rs:85-135) over an Arrow bitmap instead of byte flags -
+// the match probe's output. Count, scan, write over 64-bit words: a thread takes one word
+// of 64 rows (popcount), the tile totals go through the scan of select_rows, and the write
+// places each set bit at its rank within the word.
+// ---------------------------------------------------------------------------
+constexpr int kSbThreads = 256;  // words per tile (16384 rows)
+
+// word j of the selection: bit i = (bit bit_offset + 64 j + i of the bitmap == want) for
+// 64 j + i < n, else 0. The bitmap starts at any byte and any bit: the word is cut out of the
+// one or two 8-byte aligned words that hold its bits (the second is read only when some
+// needed bit lies in it, so no aligned word without a bit of the range is touched).
+__device__ __forceinline__ unsigned long long select_word(const uint8_t* __restrict__ bitmap, int64_t bit_offset,
+                                                          int64_t n, int64_t j, bool want) {
+    const int64_t i0 = j << 6;
+    if (i0 >= n) return 0;
+    const int64_t m = n - i0 < 64 ? n - i0 : 64;
+    const int64_t b = bit_offset + i0;
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(bitmap) + (uintptr_t)(b >> 3);
+    const unsigned long long* p = reinterpret_cast<const unsigned long long*>(addr & ~(uintptr_t)7);
+    const unsigned shift = (unsigned)(addr & 7) * 8 + (unsigned)(b & 7);  // < 64
+    unsigned long long w = p[0] >> shift;
+    if ((int64_t)shift + m > 64) w |= p[1] << (64 - shift);  // shift >= 1 here
+    if (!want) w = ~w;
+    if (m < 64) w &= (1ull << m) - 1;  // the tail word
+    return w;
+}
+
+__global__ void __launch_bounds__(kSbThreads)
+select_bitmap_count_kernel(const uint8_t* __restrict__ bitmap, int64_t bit_offset, int64_t n, bool want,
+                           unsigned long long* __restrict__ tcnt) {
+    __shared__ unsigned long long s_w[kSbThreads / 64];
+    const int64_t j = (int64_t)blockIdx.x * kSbThreads + threadIdx.x;
+    const unsigned long long c = (unsigned long long)__popcll(select_word(bitmap, bit_offset, n, j, want));
+    unsigned long long tot;
+    block_excl_scan<unsigned long long>(c, s_w, &tot);
+    if (threadIdx.x == 0) tcnt[blockIdx.x] = tot;
+}
+
+__global__ void __launch_bounds__(kSbThreads)
+select_bitmap_write_kernel(const uint8_t* __restrict__ bitmap, int64_t bit_offset, int64_t n, bool want, uint32_t base,
+                           const unsigned long long* __restrict__ toff, uint32_t* __restrict__ out) {
+    __shared__ unsigned long long s_w[kSbThreads / 64];
+    const int64_t j = (int64_t)blockIdx.x * kSbThreads + threadIdx.x;
+    unsigned long long w = select_word(bitmap, bit_offset, n, j, want);
+    unsigned long long tot;
+    unsigned long long pos =
+        toff[blockIdx.x] + block_excl_scan<unsigned long long>((unsigned long long)__popcll(w), s_w, &tot);
+    const uint32_t r0 = base + (uint32_t)(j << 6);
+    while (w) {  // <= n bits are set over all words: pos stays below the capacity n
+        out[pos++] = r0 + (uint32_t)(__ffsll((long long)w) - 1);
+        w &= w - 1;
+    }
+}
+
+static int64_t select_bitmap_tiles(int64_t n) {
+    const int64_t nwords = (n + 63) >> 6;
+    return (nwords + kSbThreads - 1) / kSbThreads;
+}
+
+int64_t select_bitmap_workspace(int64_t n) {
+    const int64_t nt = select_bitmap_tiles(n);
+    return ((8 * (nt + 2) + scan_scratch_bytes(nt) + 256 + 7) / 8) * 8;
+}
+
+hipError_t launch_select_bitmap(const uint8_t* bitmap, int64_t bit_offset, int64_t n, int want, uint32_t base,
+                                uint32_t* out, int64_t* d_count, void* workspace, hipStream_t s) {
+    const int64_t nt = select_bitmap_tiles(n);
+    if (nt == 0) return hipMemsetAsync(d_count, 0, 8, s);
+    unsigned long long* tcnt = (unsigned long long*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+    void* scratch = tcnt + (nt + 2);
+    select_bitmap_count_kernel<<<(unsigned)nt, kSbThreads, 0, s>>>(bitmap, bit_offset, n, want != 0, tcnt);
+    hipError_t e = launch_scan_u64(tcnt, nt, scratch, (unsigned long long*)d_count, s);
+    if (e != hipSuccess) return e;
+    select_bitmap_write_kernel<<<(unsigned)nt, kSbThreads, 0, s>>>(bitmap, bit_offset, n, want != 0, base, tcnt, out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // gather (Arrow take). Index all-ones (UINT32_MAX / UINT64_MAX) = null index (the
 // outer joins' null build / probe side). Output validity: one wave writes the 64 bits
 // of its 64 consecutive rows with one 8-byte store (dst_valid 8-byte aligned, bit 0 =

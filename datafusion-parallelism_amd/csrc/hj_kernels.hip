@@ -4799,6 +4799,204 @@ hipError_t launch_probe(int key_bytes, const TableView& tv, const void* keys, co
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// match probe: per probe row whether, and how often, its key occurs in the table; no
+// pairs. The lookup of the pair probe (lookup4), stopped before the emission: what the
+// reference's semi and anti joins keep of get_matching_indices once get_semi_indices /
+// get_anti_indices and ConcurrentBitSet::set_ones have folded the pairs into flags
+// (src/operator/probe_lookup_implementation/right_semi.rs:74-125, left_semi.rs:112-164,
+// src/shared/datafusion_private.rs:85-135). One launch: lookup, counts, bitmap words, build
+// marks, statistics. No look-back, scan or ordering: a grid-stride loop over blocks of
+// kMatchRows rows.
+//
+// Bitmap layout. lookup4 gives a lane four consecutive rows (one 16- or 32-byte key load,
+// four bucket lines in flight per lane before the first compare), so a wave covers 256
+// rows = four bitmap words, and the lane's four match bits are a nibble of one of them.
+// The kernel keeps lookup4 - its memory-level parallelism is what a random table read
+// lives on - and assembles the words from four ballots (ballot q: bit L = row 4L + q):
+// word w = the bits 16w..16w+15 of each ballot spread to every fourth bit, OR'ed at shift
+// q. That is ~20 scalar-uniform ALU operations per 256 rows in lanes 0-3, against a
+// reload of the keys in ballot order (filter_test_kernel's layout) that would give up the
+// vector key load and three of the four lines in flight.
+//
+// Build marks (MARK). Singles and keys of <= kRunMaxRows rows (every run ref among them)
+// are marked directly: <= 9 byte stores per probe row. A larger key is claimed once per
+// call by an atomic OR into the call's own zeroed claim bitmap - indexed by the key's
+// position in a direct-addressed table, by its duplicate-segment offset / 8 in a hashed
+// one (segments of >= 10 rows are >= 11 words apart) - and only the claimer walks its
+// segment: by itself up to 64 rows, with the whole wave beyond. m probe rows of a key of c
+// rows so cost m claim tests + c stores, not m * c. The flags themselves are never the
+// claim: they may hold anything before the call, and are only ever stored 1.
+// ---------------------------------------------------------------------------
+constexpr int kMatchThreads = 256;
+constexpr int kMatchRows = kMatchThreads * 4;  // rows of one block iteration (16 bitmap words)
+constexpr int kMatchMaxBlocks = 2048;
+constexpr uint32_t kMatchLaneWalk = 64;        // a claimed segment beyond this is walked by the wave
+
+// bit j of the low 16 bits -> bit 4j
+__device__ __forceinline__ unsigned long long spread16_by4(unsigned long long x) {
+    x &= 0xFFFFull;
+    x = (x | (x << 24)) & 0x000000FF000000FFull;
+    x = (x | (x << 12)) & 0x000F000F000F000Full;
+    x = (x | (x << 6)) & 0x0303030303030303ull;
+    x = (x | (x << 3)) & 0x1111111111111111ull;
+    return x;
+}
+
+__device__ __forceinline__ void match_mark(const TableView& tv, uint32_t row, uint8_t* __restrict__ flags,
+                                           uint64_t nflags) {
+    const uint64_t id = tv.row_ids != nullptr ? tv.row_ids[row] : (uint64_t)row;
+    if (id < nflags) flags[id] = 1;  // idempotent byte stores: no atomics needed
+}
+
+// COUNTS and MARK select the optional outputs at compile time (the marking's registers and
+// the count stores leave the other instantiations); the bitmap's presence is a wave-uniform
+// test of its pointer around four ballots and one store, not worth doubling the variants.
+template <typename K, bool HAS_VALID, bool COUNTS, bool MARK>
+__global__ void __launch_bounds__(kMatchThreads)
+probe_match_kernel(TableView tv, const void* __restrict__ keys, const uint8_t* __restrict__ valid, int64_t voff,
+                   int64_t n, bool vec, unsigned long long* __restrict__ out_bitmap, uint32_t* __restrict__ out_counts,
+                   bool cvec, uint8_t* __restrict__ flags, uint64_t nflags, uint32_t* __restrict__ claim,
+                   unsigned long long* __restrict__ stats) {
+    __shared__ unsigned long long s_m[kMatchThreads / 64], s_p[kMatchThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t nwords = (n + 63) >> 6;
+    unsigned long long matched = 0, pairs = 0;
+    for (int64_t blk0 = (int64_t)blockIdx.x * kMatchRows; blk0 < n; blk0 += (int64_t)gridDim.x * kMatchRows) {
+        const int64_t wrow0 = blk0 + (int64_t)wave * 256;
+        if (wrow0 >= n) continue;  // the whole wave: no word of the bitmap starts here
+        const int64_t row0 = wrow0 + (int64_t)lane * 4;
+        uint32_t ref[4] = {kMiss, kMiss, kMiss, kMiss}, cnt[4] = {0, 0, 0, 0};
+        if (row0 < n) lookup4<K, HAS_VALID>(tv, keys, valid, voff, n, vec, row0, ref, cnt);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            cnt[q] = resolve_count(tv.dup_rows, ref[q], cnt[q], tv.off_mask);
+            matched += ref[q] != kMiss;
+            pairs += cnt[q];
+        }
+        if (out_bitmap != nullptr) {
+            unsigned long long b[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) b[q] = __ballot(ref[q] != kMiss);
+            if (lane < 4) {  // lane w assembles word w of the wave's four
+                unsigned long long word = 0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) word |= spread16_by4(b[q] >> (16 * lane)) << q;
+                const int64_t widx = (wrow0 >> 6) + lane;
+                if (widx < nwords) out_bitmap[widx] = word;  // rows >= n are kMiss: tail bits 0
+            }
+        }
+        if constexpr (COUNTS) {
+            if (cvec && row0 + 4 <= n) {
+                *reinterpret_cast<uint4*>(out_counts + row0) = make_uint4(cnt[0], cnt[1], cnt[2], cnt[3]);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (row0 + q < n) out_counts[row0 + q] = cnt[q];
+            }
+        }
+        if constexpr (MARK) {
+            bool big[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t r = ref[q], c = cnt[q];
+                big[q] = false;
+                if (r == kMiss) continue;
+                if (!(r & kDupFlag)) {
+                    match_mark(tv, r, flags, nflags);
+                } else if (c <= kRunMaxRows) {
+                    for (uint32_t j = 0; j < c; ++j)
+                        match_mark(tv, dup_ref_row(tv.dup_rows, r, tv.off_mask, j), flags, nflags);
+                } else {
+                    const uint32_t off = r & tv.off_mask;
+                    uint32_t ci = off >> 3;
+                    if (tv.dense != nullptr)  // a matched row: row0 + q < n and the key is in range
+                        ci = (uint32_t)((uint64_t)(int64_t) reinterpret_cast<const K*>(keys)[row0 + q] -
+                                        (uint64_t)tv.dmin);
+                    uint32_t* w = claim + (ci >> 5);
+                    const uint32_t bit = 1u << (ci & 31);
+                    // most rows of a hot key find it claimed: test before the read-modify-write
+                    bool mine = false;
+                    if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit))
+                        mine = !(atomicOr(w, bit) & bit);
+                    if (mine) {
+                        if (c <= kMatchLaneWalk) {
+                            for (uint32_t j = 0; j < c; ++j) match_mark(tv, tv.dup_rows[off + 1 + j], flags, nflags);
+                        } else {
+                            big[q] = true;
+                        }
+                    }
+                }
+            }
+            // segments of more than kMatchLaneWalk rows: the wave walks them one after another
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                unsigned long long m = __ballot(big[q]);
+                while (m) {
+                    const int src = __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    const uint32_t off = __shfl(ref[q] & tv.off_mask, src, 64);
+                    const uint32_t c = __shfl(cnt[q], src, 64);
+                    for (uint32_t j = lane; j < c; j += 64) match_mark(tv, tv.dup_rows[off + 1 + j], flags, nflags);
+                }
+            }
+        }
+    }
+    // statistics: wave reduction, then one atomic pair per workgroup
+    const unsigned long long wm = wave_sum<unsigned long long>(matched);
+    const unsigned long long wp = wave_sum<unsigned long long>(pairs);
+    if (lane == 0) { s_m[wave] = wm; s_p[wave] = wp; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tm = 0, tp = 0;
+        for (int w = 0; w < kMatchThreads / 64; ++w) { tm += s_m[w]; tp += s_p[w]; }
+        if (tm) atomicAdd(stats, tm);
+        if (tp) atomicAdd(stats + 1, tp);
+    }
+}
+
+int64_t probe_match_workspace(uint64_t claim_bits) {
+    return kMatchWsHeader + (int64_t)((claim_bits + 63) / 64) * 8;
+}
+
+hipError_t launch_probe_match(int key_bytes, const TableView& tv, const void* keys, const uint8_t* valid, int64_t voff,
+                              int64_t n, uint8_t* out_bitmap, uint32_t* out_counts, uint8_t* flags, int64_t nflags,
+                              int64_t* d_stats, void* workspace, uint64_t claim_bits, hipStream_t s) {
+    // workspace: [0, 16) the statistics of a caller that passes none, then the claim bitmap
+    unsigned long long* stats = reinterpret_cast<unsigned long long*>(d_stats != nullptr ? (void*)d_stats : workspace);
+    hipError_t e = hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    if (n <= 0) return hipSuccess;
+    const bool mark = flags != nullptr && nflags > 0;
+    uint32_t* claim = reinterpret_cast<uint32_t*>((char*)workspace + kMatchWsHeader);
+    if (mark) {
+        e = hipMemsetAsync(claim, 0, (size_t)((claim_bits + 63) / 64) * 8, s);
+        if (e != hipSuccess) return e;
+    }
+    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15) == 0;
+    const bool cvec = (reinterpret_cast<uintptr_t>(out_counts) & 15) == 0;
+    const unsigned grid = (unsigned)std::min<int64_t>((n + kMatchRows - 1) / kMatchRows, kMatchMaxBlocks);
+    unsigned long long* bm = reinterpret_cast<unsigned long long*>(out_bitmap);
+#define DFP_MATCH(KT, HV, CN, MK)                                                                                   \
+    probe_match_kernel<KT, HV, CN, MK><<<grid, kMatchThreads, 0, s>>>(tv, keys, valid, voff, n, vec, bm, out_counts, \
+                                                                      cvec, flags, (uint64_t)nflags, claim, stats)
+#define DFP_MATCH_K(KT, HV)                                          \
+    do {                                                             \
+        if (out_counts && mark) DFP_MATCH(KT, HV, true, true);       \
+        else if (out_counts) DFP_MATCH(KT, HV, true, false);         \
+        else if (mark) DFP_MATCH(KT, HV, false, true);               \
+        else DFP_MATCH(KT, HV, false, false);                        \
+    } while (0)
+    if (key_bytes == 8) {
+        if (valid) DFP_MATCH_K(int64_t, true); else DFP_MATCH_K(int64_t, false);
+    } else {
+        if (valid) DFP_MATCH_K(int32_t, true); else DFP_MATCH_K(int32_t, false);
+    }
+#undef DFP_MATCH_K
+#undef DFP_MATCH
+    return hipGetLastError();
+}
+
 // A gathered direct-addressed table (the sharded-build broadcast plan): each piece's
 // duplicated-key refs point into its own segment array; once the pieces' segment arrays
 // sit one after another, the refs of one piece move by that piece's base. Streams the

@@ -100,6 +100,21 @@ hipError_t launch_probe(int key_bytes, const TableView& tv, const void* keys, co
                         uint32_t* out_p, int64_t cap, int64_t* d_total, void* workspace,
                         hipEvent_t built, hipStream_t s);
 
+// ---- match probe -----------------------------------------------------------
+// Per probe row whether (out_bitmap: ceil(n / 64) u64 words, every word written whole, bits
+// >= n zero) and how often (out_counts u32[n]) its key occurs; flags[id] = 1 for every build
+// row a pair of the probe would name (ids >= nflags skipped, nothing cleared); d_stats[0] =
+// set bits, d_stats[1] = pairs. Every output is optional. workspace (8-byte aligned):
+// probe_match_workspace(claim_bits) bytes = kMatchWsHeader (the statistics of a caller that
+// passes no d_stats) + the claim bitmap, zeroed here when flags are given. claim_bits: the
+// table's key range (direct-addressed) or its duplicate-segment words / 8 + 1 (hashed).
+// The caller has ordered `s` after the build.
+constexpr int64_t kMatchWsHeader = 16;
+int64_t probe_match_workspace(uint64_t claim_bits);
+hipError_t launch_probe_match(int key_bytes, const TableView& tv, const void* keys, const uint8_t* valid, int64_t voff,
+                              int64_t n, uint8_t* out_bitmap, uint32_t* out_counts, uint8_t* flags, int64_t nflags,
+                              int64_t* d_stats, void* workspace, uint64_t claim_bits, hipStream_t s);
+
 // ---- table queries -------------------------------------------------------
 // refs[v] of a duplicated key (bit 31, not kMiss): offset field (mask) + base, v < n
 hipError_t launch_dense_rebase(uint32_t* refs, uint64_t n, uint32_t base, uint32_t mask, hipStream_t s);
@@ -143,6 +158,11 @@ hipError_t launch_mark_rows(const void* idx, int idx_bytes, int64_t n, uint8_t* 
 int64_t select_workspace(int64_t n);
 hipError_t launch_select_rows(const uint8_t* flags, int64_t n, uint8_t want, uint64_t* out, int64_t* d_count,
                               void* workspace, hipStream_t s);
+// ascending base + i, i < n, with bit (bit_offset + i) of the Arrow bitmap == want (0 / 1);
+// out: capacity n; workspace: select_bitmap_workspace(n)
+int64_t select_bitmap_workspace(int64_t n);
+hipError_t launch_select_bitmap(const uint8_t* bitmap, int64_t bit_offset, int64_t n, int want, uint32_t base,
+                                uint32_t* out, int64_t* d_count, void* workspace, hipStream_t s);
 hipError_t launch_gather_fixed(const void* src, const uint8_t* src_valid, int64_t src_voff, int elem_bytes,
                                const void* idx, int idx_bytes, int64_t n, void* dst, uint8_t* dst_valid,
                                hipStream_t s);

@@ -51,7 +51,8 @@ import pyarrow.compute as pc
 import torch
 
 from ._lib import HjError, HJ_ERR_INVALID
-from .columns import DeviceColumn, DeviceRecordBatch, composite_keys, filter_equal_pairs, mark_rows, select_rows
+from .columns import (DeviceColumn, DeviceRecordBatch, composite_keys, filter_equal_pairs, mark_rows, select_bitmap,
+                      select_rows)
 from .key_filter import KeyFilter
 from .table import HashTable
 
@@ -215,9 +216,10 @@ class _SharedBuild:
     """State shared by all partitions of one build (JoinStateInstances)."""
 
     def __init__(self, parallelism: int, device: int, devices: Sequence[int] | None = None, plan: str = "auto",
-                 prefilter: bool = False):
+                 prefilter: bool = False, match_probe: bool = False):
         self.parallelism = parallelism
         self.prefilter = prefilter      # probes go through a key filter over the build keys
+        self.match_probe = match_probe  # semi / anti joins probe for matches, not pairs (probe_batch)
         self._filter: KeyFilter | None = None
         self.device = devices[0] if devices else device
         self.devices = list(devices) if devices else None
@@ -306,10 +308,21 @@ class BuildImplementation:
 
     def __init__(self, build_implementation_version: JoinReplacement, parallelism: int,
                  input_schema: pa.Schema | None = None, device: int = 0, devices: Sequence[int] | None = None,
-                 plan: str = "auto", prefilter: bool = False):
+                 plan: str = "auto", prefilter: bool = False, match_probe: bool = False):
         """prefilter: every probe first drops the rows a key filter over the build keys
         rejects (KeyFilter; same output for every join type: the filter only removes rows
         that have no pair).
+        match_probe: LeftSemi, LeftAnti, RightSemi and RightAnti probe batches ask the table
+        only whether each row has a partner (HashTable.probe_match: a bitmap and the build
+        marks, no pairs) when the join has no filter, its key is one Int32/Int64 column and
+        the table lives on one device; every other case silently takes the pair path. The
+        output is the same. The match path does not use the key filter: with prefilter=True
+        too, the filter serves only the probes that take the pair path. Off by default: the
+        match path reads the table at random where the pair path's sliced probe reads it out
+        of LDS, and on large uniform joins it measured slower (C2 RightSemi 1.16 ms against
+        0.89 ms, LeftSemi 1.61 against 1.55 ms). It wins where keys repeat: a
+        key of c build rows hit by m probe rows costs m + c, not m * c (1000 rows per key:
+        0.08 ms against 22.9 ms), and it runs joins whose pairs no buffer holds.
         devices: build one table over these GPUs of the node (hj_build_begin_multi;
         DataFusion runs every partition in one process, so the in-process multi-GPU table
         is the drop-in's node-wide form); plan "auto" | "broadcast" | "radix" (the build
@@ -322,7 +335,7 @@ class BuildImplementation:
         if devices is not None and len(devices) < 1:
             raise HjError(HJ_ERR_INVALID, "devices must name at least one GPU")
         self.parallelism = parallelism
-        self._shared = _SharedBuild(parallelism, device, devices, plan, prefilter)
+        self._shared = _SharedBuild(parallelism, device, devices, plan, prefilter, match_probe)
         self._shared.schema = input_schema
 
     def build_side(self, partition: int, stream: Iterable[pa.RecordBatch], build_expressions: Sequence[str | int],
@@ -388,6 +401,20 @@ def _apply_filter(flt: JoinFilter, build_cols: list[DeviceColumn], build_names: 
     return b[rows], p[rows]
 
 
+_MATCH_JOINS = (JoinType.LeftSemi, JoinType.LeftAnti, JoinType.RightSemi, JoinType.RightAnti)
+
+
+def _takes_match_path(jt: JoinType, filter, lookup: GpuIndexLookup, key_cols: Sequence[DeviceColumn], n: int) -> bool:
+    """BuildImplementation(match_probe=True): a semi / anti join without a filter, keyed by
+    one Int32/Int64 column (a composite key's 64-bit hash needs the equality re-check on
+    pairs), on a one-device table."""
+    sh = lookup._shared
+    return (sh is not None and sh.match_probe and jt in _MATCH_JOINS and filter is None and n > 0
+            and not sh.composite and len(key_cols) == 1
+            and (pa.types.is_int64(key_cols[0].type) or pa.types.is_int32(key_cols[0].type))
+            and lookup.table.devices is None)
+
+
 def probe_batch(join_type: JoinType, probe_expressions: Sequence[str | int], build_expressions: Sequence[str | int],
                 filter: JoinFilter | None, build_side_records: pa.RecordBatch, read_only_join_map: GpuIndexLookup,
                 probe_batch: pa.RecordBatch, build_visited: torch.Tensor | None = None) -> pa.RecordBatch | None:
@@ -403,6 +430,17 @@ def probe_batch(join_type: JoinType, probe_expressions: Sequence[str | int], bui
     probe_cols = [DeviceColumn.from_arrow(c, dev) for c in probe_batch.columns]
     key_cols = [probe_cols[e if isinstance(e, int) else probe_batch.schema.get_field_index(e)]
                 for e in probe_expressions]
+    if _takes_match_path(jt, filter, lookup, key_cols, n):
+        # no pairs: the matched-probe bitmap (get_semi_indices / get_anti_indices) and the
+        # visited build rows (set_ones) straight from the lookup
+        k = key_cols[0]
+        left = jt in (JoinType.LeftSemi, JoinType.LeftAnti)
+        m = lookup.table.probe_match(k.key_tensor(), k.valid, valid_offset=k.voff,
+                                     build_flags=build_visited if left else None)
+        if left:
+            return None
+        rows = select_bitmap(m.bitmap, n, 1 if jt is JoinType.RightSemi else 0)
+        return _batch([c.take(rows) for c in probe_cols], list(probe_batch.schema.names))
     b, p = lookup.matching_indices_device(key_cols, build_side_records)
     build_cols = lookup.build_columns(build_side_records)
     bnames, pnames = list(build_side_records.schema.names), list(probe_batch.schema.names)
@@ -518,9 +556,12 @@ class ParallelHashJoin:
                  on: Sequence[tuple[str, str]], join_type: JoinType | str = JoinType.Inner, device: int = 0,
                  replacement: JoinReplacement = JoinReplacement.Gpu, filter: JoinFilter | None = None,
                  right_schema: pa.Schema | None = None, devices: Sequence[int] | None = None, plan: str = "auto",
-                 prefilter: bool = False):
+                 prefilter: bool = False, match_probe: bool = False):
         """devices / plan: one build table over several GPUs (BuildImplementation);
-        prefilter: probe through a key filter over the build keys (BuildImplementation)."""
+        prefilter: probe through a key filter over the build keys (BuildImplementation);
+        match_probe: semi and anti joins without a filter, on one Int32/Int64 key and one
+        device, probe for matches instead of pairs (BuildImplementation; same output; the
+        match path ignores the key filter; other joins silently take the pair path)."""
         if len(on) < 1:
             raise HjError(HJ_ERR_INVALID, "an equi-join needs at least one (left, right) key pair")
         self.join_type = JoinType.parse(join_type)
@@ -532,7 +573,7 @@ class ParallelHashJoin:
         self.filter = filter
         self.right_schema = right_schema or next((b.schema for part in self.right for b in part), None)
         self._build = BuildImplementation(replacement, n, device=device, devices=devices, plan=plan,
-                                          prefilter=prefilter)
+                                          prefilter=prefilter, match_probe=match_probe)
         self._finalizer = _Finalizer(n)
 
     def execute(self, partition: int) -> list[pa.RecordBatch]:

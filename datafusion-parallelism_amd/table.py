@@ -114,6 +114,32 @@ def is_budget_error(e: Exception) -> bool:
     return isinstance(e, _lib.HjError) and e.status == _lib.HJ_ERR_OOM and "device budget" in str(e)
 
 
+class MatchResult:
+    """Result of HashTable.probe_match: `bitmap` (uint8 device tensor, an Arrow LSB bitmap of
+    ceil(n/64)*8 bytes, bit i = row i has a partner; usable as a `valid` bitmap), `counts`
+    (int32 device tensor of the rows' pair counts, the bits of a uint32; or None) and the
+    lazily read statistics `matched` and `pairs` (the only host synchronisation)."""
+
+    def __init__(self, n: int, bitmap: torch.Tensor, counts: torch.Tensor | None, d_stats: torch.Tensor):
+        self.n, self.bitmap, self.counts, self._d_stats, self._stats = n, bitmap, counts, d_stats, None
+
+    def _read(self) -> tuple[int, int]:
+        if self._stats is None:
+            m, p = self._d_stats.cpu().tolist()
+            self._stats = (int(m), int(p))
+        return self._stats
+
+    @property
+    def matched(self) -> int:
+        """Probe rows with a partner (set bits of the bitmap)."""
+        return self._read()[0]
+
+    @property
+    def pairs(self) -> int:
+        """Pairs an inner probe of the same rows would produce (may exceed 2^32)."""
+        return self._read()[1]
+
+
 class HashTable:
     """One shared build table for `parallelism` partitions (hj_build_begin .. finish)."""
 
@@ -335,6 +361,52 @@ class HashTable:
         else:
             check(self._L.hj_probe_async_ids(self._h, keys_ptr, valid_ptr, voff, probe_ids_ptr, n, out_build_ptr,
                                              out_probe_ptr, capacity, d_total_ptr, workspace_ptr, stream or None))
+
+    # -- match probe (hj_probe_match): matches and counts without pairs -------------------
+    def match_workspace_bytes(self, n: int) -> int:
+        """hj_probe_match_workspace_bytes (depends on the table's layout; no device work)."""
+        v = self._L.hj_probe_match_workspace_bytes(self._h, int(n))
+        if v < 0:
+            check(_lib.HJ_ERR_INVALID, self._L)
+        return v
+
+    def probe_match_async(self, keys_ptr: int, n: int, bitmap_ptr: int | None, workspace_ptr: int, stream: int = 0,
+                          valid_ptr: int | None = None, voff: int = 0, counts_ptr: int | None = None,
+                          build_flags_ptr: int | None = None, nflags: int = 0, d_stats_ptr: int | None = None) -> None:
+        """hj_probe_match on raw device pointers (no sync, no allocation); every output
+        pointer is optional."""
+        check(self._L.hj_probe_match(self._h, keys_ptr or None, valid_ptr, voff, n, bitmap_ptr, counts_ptr,
+                                     build_flags_ptr, nflags, d_stats_ptr, workspace_ptr, stream or None), self._L)
+
+    def probe_match(self, keys: torch.Tensor, valid=None, valid_offset: int = 0, counts: bool = False,
+                    build_flags: torch.Tensor | None = None) -> "MatchResult":
+        """Per probe row whether (and, with counts=True, how often) its key occurs in the
+        table, without materialising pairs: what a semi or anti join needs. keys: a device
+        tensor; valid: bool mask or LSB bitmap from bit valid_offset (as_key_input);
+        build_flags: a uint8 device tensor, one byte per build row (or id), updated in place:
+        the rows the probe's pairs would name are set to 1, nothing is cleared, so one
+        tensor accumulates over batches. Not for a multi-GPU table (HJ_ERR_INVALID). No
+        host synchronisation: MatchResult.matched / .pairs read the statistics lazily."""
+        if not (isinstance(keys, torch.Tensor) and keys.is_cuda):
+            raise TypeError("probe_match takes a device tensor of keys")
+        ki = as_key_input(keys, valid, valid_offset)
+        if ki.n and ki.key_type != self.key_type:
+            raise TypeError("probe key type differs from the build key type")
+        if build_flags is not None and not (build_flags.is_cuda and build_flags.dtype == torch.uint8 and
+                                            build_flags.is_contiguous()):
+            raise TypeError("build_flags must be a contiguous uint8 device tensor")
+        dev = keys.device
+        n = ki.n
+        bitmap = torch.empty(((n + 63) // 64) * 8, dtype=torch.uint8, device=dev)
+        cnt = torch.empty(n, dtype=torch.int32, device=dev) if counts else None
+        d_stats = torch.empty(2, dtype=torch.int64, device=dev)
+        ws = torch.empty(self.match_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        self.probe_match_async(ki.ptr, n, bitmap.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream,
+                               ki.valid_ptr, ki.voff, None if cnt is None else cnt.data_ptr(),
+                               None if build_flags is None else build_flags.data_ptr(),
+                               0 if build_flags is None else build_flags.numel(), d_stats.data_ptr())
+        # ws and the key tensors are released in stream order by torch's allocator
+        return MatchResult(n, bitmap, cnt, d_stats)
 
     # -- sharded-build broadcast plan (hj_table_dense_piece / hj_table_wrap_dense) -------
     def dense_piece(self) -> dict:

@@ -279,6 +279,53 @@ hj_status hj_probe_async_base(const hj_table* t, const void* keys, const uint8_t
                               uint64_t* out_build, uint32_t* out_probe, int64_t capacity,
                               int64_t* d_total, void* workspace, void* stream);
 
+/* Match probe: per probe row, whether and how often its key occurs in the table, with no
+ * pairs. Replaces get_matching_indices followed by get_semi_indices / get_anti_indices or
+ * ConcurrentBitSet::set_ones where only the fact of a match is kept - the semi and anti
+ * joins (src/operator/probe_lookup_implementation/right_semi.rs:74-125,
+ * left_semi.rs:112-164, src/shared/datafusion_private.rs:85-135) - and serves sizing
+ * (per-row pair counts before any pair is written). Opt-in: nothing else in the library
+ * calls it. Device pointers, asynchronous on `stream`, no host synchronisation, no
+ * allocation; one launch.
+ *
+ * Every output is defined through the pair probe. Let S be the pairs hj_probe_async would
+ * produce for the same table, keys, validity and n at unlimited capacity.
+ *   out_bitmap   (optional) Arrow LSB bitmap, 8-byte aligned, ceil(n/64)*8 bytes. Bit i is
+ *                set iff some pair of S has probe_idx == i. Every word is written in full
+ *                and bits at and beyond n are 0: the caller does not zero it. Null rows
+ *                are 0, so an anti join keeps them (the reference's KAT lib.rs:512-575).
+ *                It can be handed to any hj_probe* as `validity`, like the key filter's.
+ *   out_counts   (optional) uint32[n]: out_counts[i] = pairs of S with probe_idx == i, for
+ *                every i < n (zeros are written).
+ *   build_flags  (optional; nflags entries) byte flags as hj_mark_rows takes. After the
+ *                call they equal their value before it OR'ed with what
+ *                hj_mark_rows(S.build_idx, 8, |S|, build_flags, nflags) would set, for
+ *                arbitrary prior contents: with explicit build ids the flags are indexed by
+ *                id, ids >= nflags are skipped. Flags are never cleared and only ever
+ *                stored 1, so a caller accumulates over probe batches and over concurrent
+ *                calls on different streams (each with its own workspace).
+ *   d_stats      (optional) device int64[2], overwritten whichever other outputs are null:
+ *                d_stats[0] = set bits of the bitmap, d_stats[1] = |S| (may exceed 2^32
+ *                and the size of any buffer).
+ * Cost of marking: O(n + build rows marked) device work, not O(|S|). Keys of up to 9 rows
+ * are marked directly; a larger key is claimed once per call in a bitmap inside
+ * `workspace` that the call zeroes, and only the claimer walks its rows - a key of c rows
+ * hit by m rows of one call costs m + c, not m * c, stores. build_flags is never the claim.
+ * `workspace`: device, 8-byte aligned, hj_probe_match_workspace_bytes(t, n) bytes (depends
+ * on the table's layout: no GPU work, but waits for a pending layout to settle; -1 for a
+ * table hj_probe_match rejects or n outside [0, 2^32)); not shared by concurrent calls.
+ * Tables: every one-device table - direct-addressed (plain, packed counts, run refs),
+ * hashed, hj_table_wrap_dense tables, tables with explicit ids (HJ_IDS_U31 or not). A
+ * multi-GPU table (hj_build_begin_multi) returns HJ_ERR_INVALID. The call orders itself
+ * after the build and hj_table_free waits for it. n < 2^32; n == 0 is valid and still
+ * writes d_stats. Errors: a null, unbuilt or failed table as every probe; a null or
+ * misaligned workspace, a misaligned out_bitmap / out_counts / d_stats: HJ_ERR_INVALID. */
+int64_t hj_probe_match_workspace_bytes(const hj_table* t, int64_t n);
+hj_status hj_probe_match(const hj_table* t, const void* keys, const uint8_t* validity,
+                         int64_t validity_offset, int64_t n, uint8_t* out_bitmap,
+                         uint32_t* out_counts, uint8_t* build_flags, int64_t nflags,
+                         int64_t* d_stats, void* workspace, void* stream);
+
 /* Probe strategy for later probes of this process: 0 auto (sliced for tables past the L2s
  * - more than 2^20 key values or 2^16 buckets, at most 4 passes of 2047 slices - with a
  * probe side at least as large as the key range / bucket count, else fused),
@@ -421,6 +468,19 @@ hj_status hj_mark_rows(const void* idx, int idx_bytes, int64_t n, uint8_t* flags
 int64_t hj_select_workspace_bytes(int64_t n);
 hj_status hj_select_rows(const uint8_t* flags, int64_t n, int want, uint64_t* out,
                          int64_t* d_count, void* workspace, void* stream);
+
+/* Ascending positions of an Arrow bitmap whose bit equals `want` (0 or 1): out_rows
+ * (capacity n) receives base + i for every i < n whose bit bit_offset + i equals want,
+ * *d_count (device int64, 8-byte aligned) their number. get_semi_indices (want 1) /
+ * get_anti_indices (want 0) (src/shared/datafusion_private.rs:85-135) over a bitmap - the
+ * match probe's - instead of byte flags. bit_offset >= 0 need not be a multiple of 8, the
+ * bitmap need not be aligned; base + n <= 2^32. workspace: device, 8-byte aligned,
+ * hj_select_bitmap_workspace_bytes(n). Bad arguments, null or misaligned pointers:
+ * HJ_ERR_INVALID; no GPU: HJ_ERR_NO_DEVICE. */
+int64_t hj_select_bitmap_workspace_bytes(int64_t n);
+hj_status hj_select_bitmap(const uint8_t* bitmap, int64_t bit_offset, int64_t n, int want,
+                           uint32_t base, uint32_t* out_rows, int64_t* d_count, void* workspace,
+                           void* stream);
 
 /* Arrow take of a fixed-width column (elem_bytes 1/2/4/8/16) by indices:
  * dst[i] = src[idx[i]]; dst_valid (optional, 8-byte aligned, ceil(n/64)*8 bytes) gets
