@@ -91,6 +91,8 @@ struct BuildResources {
     int64_t* h_minmax = nullptr;
     int64_t* d_mbox = nullptr;  // its device address
     int64_t mb_seq = 0;
+    // anchor build (AnchorArgs::flag): a device word, zero between builds
+    unsigned long long* d_aflag = nullptr;
 };
 std::mutex g_pool_mu;
 std::unordered_map<int, std::vector<BuildResources>> g_pool;
@@ -126,7 +128,9 @@ bool acquire_resources(int dev, BuildResources* r) {
            hipEventCreateWithFlags(&r->evp, probe_ev_flags()) == hipSuccess &&
            hipHostMalloc((void**)&r->h_minmax, 4 * sizeof(int64_t), hipHostMallocCoherent | hipHostMallocMapped) ==
                hipSuccess &&
-           hipHostGetDevicePointer((void**)&r->d_mbox, r->h_minmax, 0) == hipSuccess;
+           hipHostGetDevicePointer((void**)&r->d_mbox, r->h_minmax, 0) == hipSuccess &&
+           hipMalloc((void**)&r->d_aflag, 64) == hipSuccess && hipMemset(r->d_aflag, 0, 64) == hipSuccess &&
+           hipStreamSynchronize(nullptr) == hipSuccess;  // zero before any build stream reads it
 }
 
 void release_resources(int dev, const BuildResources& r) {
@@ -347,6 +351,15 @@ bool spec_build_on() {
     }();
     return v;
 }
+// DFP_HJ_ANCHOR_BUILD=0: the speculative dense build reduces the key range before its
+// partition (key_minmax_part_kernel + minmax_final_kernel), as before the anchor build
+bool anchor_build_on() {
+    static const bool v = [] {
+        const char* e = getenv("DFP_HJ_ANCHOR_BUILD");
+        return !(e != nullptr && e[0] == '0');
+    }();
+    return v;
+}
 double load_factor() {
     const char* e = getenv("DFP_HJ_LOAD_FACTOR");
     double lf = e ? atof(e) : kDefaultLoadFactor;
@@ -402,6 +415,9 @@ struct hj_table {
     bool packed = false;        // dense refs with inline counts (dup_rows offsets < 2^27)
     int64_t dmin = 0;
     uint64_t drange = 0;
+    // anchor build: refs[0] is the key (min >> 13) << 13; the exact minimum is dmin + dskip
+    // (what hj_table_dense_piece / _export and the statistics report)
+    uint64_t dskip = 0;
     bool has_range = false;     // hj_build_key_range: the caller's key range replaces the reduction
     bool force_dense = false;   // hj_build_dense: direct-addressed over that range whatever the density
     int64_t range_lo = 0, range_hi = 0;
@@ -430,6 +446,7 @@ struct hj_table {
     std::mutex spec_mu;
     int64_t spec_seq = 0;
     uint32_t spec_cap = 0;
+    bool spec_anchor = false;          // the range comes from the partition; blocks aligned to 8192
     const int64_t* spec_mm = nullptr;  // the reduction's result in device memory (scratch)
     std::vector<Segment> spec_segs;    // the build's segments, for a build in another layout
     bool mm_known = false;             // the key range read after a speculative build
@@ -558,6 +575,18 @@ hj_status build_attempt(hj_table* t, const std::vector<Segment>& segs, double lf
     const ChunkGeom spec_g{0, 0, spec_cap << kDenseBlockShift, kDenseShift, 0, 1, packed_ok ? 1 : 0};
     const bool spec = minmax && spec_build_on() && !t->has_base && !t->force_dense && t->multi == nullptr &&
                       device_budget() <= 0 && frag_build_mode() && spec_cap > 0 && frag_build_ok(spec_g, ftiles);
+    // Anchor build: no reduction before the partition, which bins by 8192-value blocks
+    // relative to the first build key and leaves each tile's key range (hj_device.h). The
+    // anchor must be a valid key the kernels can read at once: a first (non-empty) segment
+    // with a validity bitmap keeps the reduction.
+    const Segment* aseg = nullptr;
+    for (const Segment& sg : segs)
+        if (sg.n > 0) {
+            aseg = &sg;
+            break;
+        }
+    const bool anchor = spec && anchor_build_on() && aseg != nullptr && aseg->valid == nullptr;
+    t->dskip = 0;
     // layout: a dense key range gets the direct-addressed table (one u32 ref per key value)
     ChunkGeom g{};
     bool dense = false;
@@ -570,11 +599,13 @@ hj_status build_attempt(hj_table* t, const std::vector<Segment>& segs, double lf
         if (minmax) {
             int64_t* mb = t->res.h_minmax;
             const int64_t seq = ++t->res.mb_seq;
-            HIP_TRY(launch_key_minmax(t->key_bytes, segs.data(), d_segs, (int)segs.size(), by_arg ? ctr : nullptr,
-                                      total, d_minmax, t->res.d_mbox, seq, s));
+            if (!anchor)  // (the anchor build's fold publishes the range: launch_build_frag)
+                HIP_TRY(launch_key_minmax(t->key_bytes, segs.data(), d_segs, (int)segs.size(), by_arg ? ctr : nullptr,
+                                          total, d_minmax, t->res.d_mbox, seq, s));
             if (spec) {
                 t->spec_seq = seq;
                 t->spec_cap = spec_cap;
+                t->spec_anchor = anchor;
                 t->spec_mm = d_minmax;
                 t->spec_segs = segs;
                 mm[0] = 1;  // not read: the geometry below is spec_g's
@@ -670,7 +701,7 @@ hj_status build_attempt(hj_table* t, const std::vector<Segment>& segs, double lf
         uint64_t* ids32 = nullptr;
         BigSeg* fbig;
         const int64_t fbytes =
-            frag ? frag_build_scratch_bytes(g, ftiles, total) : hashed_frag_scratch_bytes(g, hftiles, total);
+            frag ? frag_build_scratch_bytes(g, ftiles, total, anchor) : hashed_frag_scratch_bytes(g, hftiles, total);
         if ((st = dev_alloc(t, t->scratch, &fscr, (size_t)fbytes)) != HJ_OK) return st;
         if ((st = dev_alloc(t, t->scratch, &p, sizeof(uint32_t) * (size_t)(frag ? ftiles : hftiles))) != HJ_OK)
             return st;
@@ -697,9 +728,13 @@ hj_status build_attempt(hj_table* t, const std::vector<Segment>& segs, double lf
         if (frag) {
             HIP_TRY(launch_build_frag(t->key_bytes, segs.data(), (int)segs.size(), g, ftiles, fscr, d_tb, ids32,
                                       t->dense, t->dup_rows, fbig, ctr, d_segs, total, ids_as_rows, cus,
-                                      spec ? SpecGeo{(const long long*)d_minmax, (uint64_t)total, spec_cap}
+                                      spec ? SpecGeo{(const long long*)d_minmax, (uint64_t)total, spec_cap,
+                                                     anchor ? 1u : 0u}
                                            : SpecGeo{nullptr, 0, 0},
-                                      s));
+                                      s,
+                                      anchor ? AnchorArgs{aseg->keys, t->res.d_aflag, (long long*)d_minmax}
+                                             : AnchorArgs{},
+                                      t->res.d_mbox, t->spec_seq, by_arg));
             // a direct-addressed build cannot overflow (no retry): nothing to read back, the
             // build stays asynchronous; consumers wait on its completion event
             if (spec) t->spec_pending.store(true, std::memory_order_release);
@@ -801,10 +836,12 @@ hj_status ensure_geometry(const hj_table* ct) {
     int64_t* mb = t->res.h_minmax;
     HIP_TRY(wait_mailbox(mb, t->spec_seq, t->spec_mm, t->bstream));
     const int64_t mn = mb[0], mx = mb[1];
-    if (spec_dense_blocks(mn, mx, (uint64_t)t->total_rows, t->spec_cap) != 0) {
+    if (spec_dense_blocks(mn, mx, (uint64_t)t->total_rows, t->spec_cap, t->spec_anchor) != 0) {
         const uint64_t range = (uint64_t)mx - (uint64_t)mn + 1;
-        t->dmin = mn;
-        t->drange = range;
+        // anchor build: the table starts at the minimum's 8192-value block
+        t->dskip = t->spec_anchor ? (uint64_t)mn - (uint64_t)dense_block_base(mn) : 0;
+        t->dmin = (int64_t)((uint64_t)mn - t->dskip);
+        t->drange = range + t->dskip;
         t->nchunks = (uint32_t)((range + (1u << kDenseShift) - 1) >> kDenseShift);
         t->spec_pending.store(false, std::memory_order_release);
         return HJ_OK;
@@ -1745,9 +1782,9 @@ hj_status hj_table_dense_piece(const hj_table* t, uint32_t** refs, uint64_t* nva
     if (!refs || !nvalues || !key_min || !dup_rows || !dup_used || !packed) return fail(HJ_ERR_INVALID, "null out");
     if (t->multi != nullptr || t->dense == nullptr || t->ctr == nullptr || t->wrapped)
         return fail(HJ_ERR_INVALID, "hj_table_dense_piece: not a built direct-addressed single-device table");
-    *refs = t->dense;
-    *nvalues = t->drange;
-    *key_min = t->dmin;
+    *refs = t->dense + t->dskip;
+    *nvalues = t->drange - t->dskip;
+    *key_min = (int64_t)((uint64_t)t->dmin + t->dskip);
     *dup_rows = t->dup_rows;
     *dup_used = reinterpret_cast<const uint64_t*>(&t->ctr->dup_used);
     *packed = t->packed ? 1 : 0;
@@ -1760,7 +1797,8 @@ hj_status hj_table_dense_export(const hj_table* t, uint32_t* refs_dst, uint64_t 
     if (st != HJ_OK) return st;
     if (t->multi != nullptr || t->dense == nullptr || t->ctr == nullptr || t->wrapped)
         return fail(HJ_ERR_INVALID, "hj_table_dense_export: not a built direct-addressed single-device table");
-    if (refs_dst != nullptr && (v0 > t->drange || n > t->drange - v0))
+    const uint64_t xrange = t->drange - t->dskip;  // the exact key range
+    if (refs_dst != nullptr && (v0 > xrange || n > xrange - v0))
         return fail(HJ_ERR_INVALID, "hj_table_dense_export: refs range past the table's key range");
     if (dup_dst != nullptr && dup_n > (uint64_t)(2 * t->total_rows + 2))
         return fail(HJ_ERR_INVALID, "hj_table_dense_export: more segment words than the table holds");
@@ -1768,7 +1806,7 @@ hj_status hj_table_dense_export(const hj_table* t, uint32_t* refs_dst, uint64_t 
     hipStream_t s = (hipStream_t)stream;
     if (s != t->bstream) HIP_TRY(hipStreamWaitEvent(s, t->res.ev1, 0));  // after the build
     if (refs_dst != nullptr && n > 0)
-        HIP_TRY(hipMemcpyAsync(refs_dst, t->dense + v0, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(refs_dst, t->dense + t->dskip + v0, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     if (dup_dst != nullptr && dup_n > 0)
         HIP_TRY(hipMemcpyAsync(dup_dst, t->dup_rows, dup_n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     if (dup_used_dst != nullptr)

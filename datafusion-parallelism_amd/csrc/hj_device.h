@@ -182,16 +182,50 @@ constexpr uint64_t kDenseBlockValues = 8192;  // a frag-build block: 4 chunks of
 // or 0 when that range takes another layout (no valid key, wider than kDenseFactor x rows
 // or than `cap` blocks): the kernels then do nothing and the host builds once it has read
 // the range. Host and device evaluate this one function, so they agree on the outcome.
+//
+// Anchor build (SpecGeo::anchor): no reduction runs before the partition. The partition
+// bins every key by its absolute 8192-value block relative to the anchor a0 = the first
+// build key, bin = (key >> 13) - (a0 >> 13) + kAnchorBias in [0, 2 * kAnchorBias], and each
+// tile leaves its exact key range in mm[kAnchorHdr + 2 * tile ...] (AnchorArgs::part); anchor_fold_kernel
+// reduces them to mm = {min, max, lowest bin}. The table's blocks are then aligned to
+// multiples of 8192: block c is bin lo + c, refs[0] is the key (min >> 13) << 13, and the
+// aligned block count ((max >> 13) - (min >> 13) + 1, at most one more than the exact
+// range's) is what must fit `cap`. A key beyond kAnchorBias blocks from the anchor (a far
+// key) implies more than 2048 aligned blocks, i.e. another layout: its tile only reduces
+// its key range, and raises the flag so that tiles starting later skip their sort as well.
+constexpr uint32_t kDenseBlockLog = 13;
+static_assert((1ull << kDenseBlockLog) == kDenseBlockValues, "block shift");
+constexpr int64_t kAnchorBias = 2047;
+constexpr int kAnchorHdr = 4;  // int64 words of mm before the tiles' partial ranges
+struct AnchorArgs {
+    const void* keys;          // the first build key is keys[0] (a valid key)
+    unsigned long long* flag;  // nonzero once a far key was seen (left zero by the fold)
+    long long* part;           // mm, writable
+};
 struct SpecGeo {
     const long long* mm;  // null: the geometry came from the host
     uint64_t rows;
     uint32_t cap;
+    uint32_t anchor;  // anchor-relative bins, blocks aligned to multiples of 8192
 };
+static_assert(sizeof(SpecGeo) == 24, "the probe's kernels take the same arguments as before the anchor build");
+__host__ __device__ inline int64_t dense_block_base(int64_t key) {
+    return (int64_t)((uint64_t)(key >> kDenseBlockLog) << kDenseBlockLog);
+}
 __host__ __device__ inline uint32_t spec_dense_blocks(int64_t mn, int64_t mx, uint64_t rows, uint32_t cap) {
     if (mn > mx) return 0u;
     const uint64_t range = (uint64_t)mx - (uint64_t)mn + 1;  // 0: the whole int64 domain
     if (range == 0 || range > kDenseFactor * rows) return 0u;
     const uint64_t nblk = (range + kDenseBlockValues - 1) / kDenseBlockValues;
+    return nblk <= cap ? (uint32_t)nblk : 0u;
+}
+// the same with the anchor build's aligned blocks when `aligned` (the dense / other layout
+// decision stays on the exact range; only the block count that must fit `cap` differs)
+__host__ __device__ inline uint32_t spec_dense_blocks(int64_t mn, int64_t mx, uint64_t rows, uint32_t cap,
+                                                      bool aligned) {
+    if (!aligned) return spec_dense_blocks(mn, mx, rows, cap);
+    if (spec_dense_blocks(mn, mx, rows, ~0u) == 0u) return 0u;
+    const uint64_t nblk = (uint64_t)((mx >> kDenseBlockLog) - (mn >> kDenseBlockLog)) + 1;
     return nblk <= cap ? (uint32_t)nblk : 0u;
 }
 

@@ -1388,7 +1388,45 @@ __device__ __forceinline__ void hist_excl_scan_lanes(uint32_t* s_hist, uint32_t*
     __syncthreads();
 }
 
-template <typename K, bool HAS_VALID, int TL = kSlTileLog>
+// min and max of a tile's valid keys -> part[0], part[1] (LLONG_MAX, LLONG_MIN without one):
+// an anchor build's tile that does not sort (a far key; its keys come from L2 again)
+template <typename K, bool HAS_VALID, int ROWS>
+__device__ __forceinline__ void anchor_tile_range(const void* __restrict__ keys, const uint8_t* __restrict__ valid,
+                                               int64_t voff, int64_t n, int64_t tile0, long long* s_red,
+                                               long long* __restrict__ part) {
+    long long mn = LLONG_MAX, mx = LLONG_MIN;
+    for (int i = threadIdx.x; i < ROWS; i += kSlThreads) {
+        const int64_t row = tile0 + i;
+        if (row < n && (!HAS_VALID || bit_valid(valid, voff, row))) {
+            const long long k = (long long)ld_key<K>(keys, row);
+            mn = min(mn, k);
+            mx = max(mx, k);
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        mn = min(mn, (long long)__shfl_xor(mn, d, 64));
+        mx = max(mx, (long long)__shfl_xor(mx, d, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_red[2 * (threadIdx.x >> 6)] = mn;
+        s_red[2 * (threadIdx.x >> 6) + 1] = mx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kSlThreads / 64; ++w) {
+            mn = min(mn, s_red[2 * w]);
+            mx = max(mx, s_red[2 * w + 1]);
+        }
+        part[0] = mn;
+        part[1] = mx;
+    }
+}
+
+// ANCHOR (build only, hj_device.h SpecGeo): bins = 8192-value blocks relative to the first
+// build key, the tile's exact key range written beside the fragments; no key range is
+// known when the kernel runs. The probe's instantiations (ANCHOR false) compile without it.
+template <typename K, bool HAS_VALID, int TL = kSlTileLog, bool ANCHOR = false>
 // 2^14-row tiles: 8 waves per SIMD = two workgroups per CU, <= 64 VGPRs; 2^15: one (128 KB of LDS)
 __global__ void __launch_bounds__(kSlThreads, TL == 14 ? 8 : 4)
 sl_partition_kernel(int64_t dmin, uint64_t drange, uint32_t wlog, uint32_t nslices, const void* __restrict__ keys,
@@ -1402,7 +1440,32 @@ sl_partition_kernel(int64_t dmin, uint64_t drange, uint32_t wlog, uint32_t nslic
                     SpecGeo sg) {  // build with the key range on the device (mm null: dmin, drange, nslices given)
     using T = SlT<TL>;
     __shared__ __attribute__((aligned(16))) uint32_t s_ent[T::kRows];
-    if (sg.mm != nullptr) {  // (uniform) the geometry from the reduction's result; none: another layout
+    static_assert(!ANCHOR || (TL == kSlTileLog && 2 * kAnchorBias + 2 == kSlHistBins), "anchor bins fill the histogram");
+    int64_t ablk = 0;  // ANCHOR: the anchor's block - kAnchorBias
+    // ANCHOR: the build has none of the probe's outputs (their code folds away), and their
+    // arguments carry the anchor build's own (the probe's instantiations keep their argument
+    // list): hdr = the far-key flag, tcnt = the tiles' partial ranges, tent = the anchor's keys
+    const AnchorArgs aa{ANCHOR ? (const void*)tent : nullptr, ANCHOR ? hdr : nullptr,
+                        ANCHOR ? reinterpret_cast<long long*>(tcnt) : nullptr};
+    if constexpr (ANCHOR) {
+        hdr = nullptr;
+        tcnt = nullptr;
+        tent = nullptr;
+        wcnt = nullptr;
+        // (the anchor's block less the bias: a key's bin is its block minus this; scalar)
+        const int64_t a0 = ((int64_t)ld_key<K>(aa.keys, 0) >> kDenseBlockLog) - kAnchorBias;
+        ablk = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a0 >> 32)) << 32) |
+                         (uint32_t)__builtin_amdgcn_readfirstlane((int)a0));
+        nslices = kSlHistBins - 1;
+        // a far key was seen before this tile started (read once, never waited for): no sort
+        if (__hip_atomic_load(aa.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+            anchor_tile_range<K, HAS_VALID, T::kRows>(keys, valid, voff, n, (int64_t)blockIdx.x * T::kRows,
+                                                      reinterpret_cast<long long*>(s_ent),
+                                                      aa.part + kAnchorHdr + 2 * ((int64_t)blockIdx.x + tile_off));
+            return;
+        }
+    }
+    if (!ANCHOR && sg.mm != nullptr) {  // (uniform) the geometry from the reduction's result; none: another layout
         const long long mn = sg.mm[0], mx = sg.mm[1];
         const uint32_t nb = spec_dense_blocks(mn, mx, sg.rows, sg.cap);
         if (nb == 0) return;
@@ -1424,6 +1487,14 @@ sl_partition_kernel(int64_t dmin, uint64_t drange, uint32_t wlog, uint32_t nslic
     const uint32_t ebase = (tent != nullptr && hdr == nullptr) ? tent[gtile] : 0u;
     for (uint32_t b = threadIdx.x; b < kSlHistBins; b += kSlThreads) s_hist[b] = 0;
     if (threadIdx.x < T::kRanges) s_wc[threadIdx.x] = 0;
+    // ANCHOR: the tile's lowest and highest 25-bit code (bin << 13 | offset in the block) and
+    // its far-key mark, in the staging area behind the range counts
+    uint32_t* s_code = s_ent + 64;
+    if (ANCHOR && threadIdx.x == 0) {
+        s_code[0] = 0xFFFFFFFFu;
+        s_code[1] = 0u;
+        s_code[2] = 0u;
+    }
     // probe: zero the workspace header incl. the error word (no memset launch)
     // (and the emission's tile counter after the tile counts: one tile per workgroup here)
     if (hdr != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1470,6 +1541,18 @@ sl_partition_kernel(int64_t dmin, uint64_t drange, uint32_t wlog, uint32_t nslic
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int64_t row = tile0 + loc0 + q;
+                if constexpr (ANCHOR) {
+                    // both terms fit 51 bits: no overflow at either end of the int64 domain
+                    const uint64_t bin = (uint64_t)((k[q] >> kDenseBlockLog) - ablk);
+                    const bool valid_row = row < n && (!HAS_VALID || bit_valid(valid, voff, row));
+                    const bool ok = valid_row && bin <= (uint64_t)(2 * kAnchorBias);
+                    const uint32_t sl = (uint32_t)bin;
+                    const uint32_t off = (uint32_t)k[q] & (uint32_t)(kDenseBlockValues - 1);
+                    e[g][q] = (off << TL) | (uint32_t)(loc0 + q);
+                    // (a far key leaves 0xFFFFFFFE: the tile will not sort)
+                    sr[g][q] = ok ? (sl << TL) | atomicAdd(&s_hist[sl], 1u) : 0xFFFFFFFFu - (uint32_t)valid_row;
+                    continue;
+                }
                 const uint64_t idx = (uint64_t)k[q] - (uint64_t)dmin;
                 const bool ok = row < n && (!HAS_VALID || bit_valid(valid, voff, row)) && idx < drange;
                 const uint32_t sl = (uint32_t)(idx >> wlog);
@@ -1486,7 +1569,48 @@ sl_partition_kernel(int64_t dmin, uint64_t drange, uint32_t wlog, uint32_t nslic
     };
     if (vec && tile0 + T::kRows <= n && !(nt & 1)) groups(std::true_type{});
     else groups(std::false_type{});
+    if constexpr (ANCHOR) {  // the lowest and highest codes of the staged entries -> the waves' -> the tile's
+        uint32_t cmin = 0xFFFFFFFFu, cmax = 0u;
+        bool far = false;
+#pragma unroll
+        for (int g = 0; g < T::kGroups; ++g)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t code = ((sr[g][q] >> TL) << kDenseBlockLog) | (e[g][q] >> TL);
+                const bool ok = sr[g][q] < 0xFFFFFFFEu;
+                far |= sr[g][q] == 0xFFFFFFFEu;
+                cmin = min(cmin, ok ? code : 0xFFFFFFFFu);
+                cmax = max(cmax, ok ? code : 0u);
+            }
+        if (far) s_code[2] = 1u;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            cmin = min(cmin, (uint32_t)__shfl_xor((int)cmin, d, 64));
+            cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, d, 64));
+        }
+        if ((threadIdx.x & 63) == 0) {
+            atomicMin(&s_code[0], cmin);
+            atomicMax(&s_code[1], cmax);
+        }
+    }
     __syncthreads();
+    if constexpr (ANCHOR) {
+        long long* part = aa.part + kAnchorHdr + 2 * gtile;
+        if (s_code[2] != 0) {  // (uniform) a far key in this tile: its key range only, and the flag
+            if (threadIdx.x == 0) __hip_atomic_store(aa.flag, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();  // the histogram's last reads are above: it serves the reduction now
+            anchor_tile_range<K, HAS_VALID, T::kRows>(keys, valid, voff, n, tile0, reinterpret_cast<long long*>(s_hist),
+                                                      part);
+            return;
+        }
+        if (threadIdx.x == 0) {
+            const uint32_t lo = s_code[0], hi = s_code[1];
+            // code = key - the first key of bin 0
+            const uint64_t org = (uint64_t)ablk << kDenseBlockLog;
+            part[0] = lo <= hi ? (long long)(org + lo) : LLONG_MAX;  // no valid key: the identity
+            part[1] = lo <= hi ? (long long)(org + hi) : LLONG_MIN;
+        }
+    }
     // the range counts leave s_ent before the scan's barriers (its wave totals use s_ent[0, 16))
     const uint32_t my_wc = (wcnt != nullptr && threadIdx.x < T::kRanges) ? s_wc[threadIdx.x] : 0u;
     // exclusive scan of the bins, four per thread
@@ -1497,7 +1621,12 @@ sl_partition_kernel(int64_t dmin, uint64_t drange, uint32_t wlog, uint32_t nslic
         *wc = (uint16_t)((ebase ? *wc : 0u) + my_wc);
     }
     uint16_t* to = toff + gtile * (int64_t)nbins;
-    for (uint32_t b = threadIdx.x; b < nbins; b += kSlThreads) to[b] = (uint16_t)(ebase + s_hist[b]);
+    if constexpr (ANCHOR) {  // all kSlHistBins bounds: each thread's four bins in one 8-byte store
+        const uint4 h = *reinterpret_cast<const uint4*>(s_hist + threadIdx.x * 4);
+        *reinterpret_cast<uint2*>(to + threadIdx.x * 4) = make_uint2(h.x | (h.y << 16), h.z | (h.w << 16));
+    } else {
+        for (uint32_t b = threadIdx.x; b < nbins; b += kSlThreads) to[b] = (uint16_t)(ebase + s_hist[b]);
+    }
     if (tile_base != nullptr && threadIdx.x == 0) tile_base[gtile] = (uint32_t)(row_base + tile0);  // build only
     // probe: the tile's pair count starts as its entries (in-range rows); S2 adds count - 1
     // for every entry whose key is missing (-1) or duplicated (+count - 1). A later pass
@@ -1547,10 +1676,15 @@ __global__ void __launch_bounds__(256)
 sl_toff_transpose_kernel(const uint16_t* __restrict__ toff, uint32_t nbins, int64_t ntiles,
                          uint16_t* __restrict__ toffT, SpecGeo sg) {
     __shared__ uint16_t s_t[64][kSlTrChunk + 2];
+    uint32_t sbins = nbins, lo = 0;  // the source's bins per tile, and its bin of block 0
     if (sg.mm != nullptr) {  // (uniform) bins from the reduction's result; the grid covers the widest
-        const uint32_t nb = spec_dense_blocks(sg.mm[0], sg.mm[1], sg.rows, sg.cap);
+        const uint32_t nb = spec_dense_blocks(sg.mm[0], sg.mm[1], sg.rows, sg.cap, sg.anchor != 0);
         if (nb == 0) return;
-        nbins = nb + 1;
+        sbins = nbins = nb + 1;
+        if (sg.anchor) {  // anchor bins: block c is bin lo + c of the tile's kSlHistBins prefixes
+            sbins = kSlHistBins;
+            lo = (uint32_t)sg.mm[2];
+        }
     }
     const uint32_t nch = (nbins + kSlTrChunk - 1) / kSlTrChunk;
     const int64_t b = blockIdx.x / nch;
@@ -1560,7 +1694,7 @@ sl_toff_transpose_kernel(const uint16_t* __restrict__ toff, uint32_t nbins, int6
     for (uint32_t i = threadIdx.x; i < 64 * kSlTrChunk; i += 256) {
         const uint32_t j = i / kSlTrChunk, c = i % kSlTrChunk;
         const int64_t t = b * 64 + j;
-        if (c < cw) s_t[j][c] = t < ntiles ? toff[t * nbins + c0 + c] : (uint16_t)0;
+        if (c < cw) s_t[j][c] = t < ntiles ? toff[t * sbins + lo + c0 + c] : (uint16_t)0;
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < 64 * kSlTrChunk; i += 256) {
@@ -1600,9 +1734,9 @@ dense_frag_build_kernel(ChunkGeom g, uint32_t nblk, int64_t ntiles, const uint16
     constexpr uint32_t NSUB = GV / kDenseSub;
     __shared__ uint32_t refs[GV];
     if (sg.mm != nullptr) {  // (uniform) blocks from the reduction's result; the grid covers `cap`
-        const uint32_t nb = spec_dense_blocks(sg.mm[0], sg.mm[1], sg.rows, sg.cap);
+        const uint32_t nb = spec_dense_blocks(sg.mm[0], sg.mm[1], sg.rows, sg.cap, sg.anchor != 0);
         if (blockIdx.x >= nb) return;
-        g.dmin = sg.mm[0];
+        g.dmin = sg.anchor ? dense_block_base(sg.mm[0]) : sg.mm[0];  // anchor build: aligned blocks
         nblk = nb;
     }
     __shared__ uint32_t d_off[kDenseSub], d_cur[kDenseSub], d_cnt[kDenseSub];
@@ -4059,6 +4193,53 @@ __global__ void __launch_bounds__(1024) minmax_final_kernel(long long* out, unsi
     }
 }
 
+// Anchor build (hj_device.h SpecGeo): the partition's tiles left their exact key ranges in
+// mm[kAnchorHdr + 2 * tile ...]; one workgroup reduces them to mm = {min, max, lowest bin}
+// and publishes the range through the host mailbox, as minmax_final_kernel does. It also
+// does what the reduction's first block did for the kernels after it (the segments to
+// d_segs, the counters zeroed: ctr non-null), and lowers the far-key flag for the next build.
+template <typename K>
+__global__ void __launch_bounds__(1024)
+anchor_fold_kernel(long long* mm, unsigned ntiles, const void* __restrict__ akeys, unsigned long long* aflag,
+                   long long* mbox, long long seq, Segment* segs, SegArgs sa, int nseg, BuildCounters* ctr) {
+    __shared__ long long s_mn[16], s_mx[16];
+    if (ctr != nullptr) {
+        if (threadIdx.x < (unsigned)nseg) segs[threadIdx.x] = sa.s[threadIdx.x];
+        if (threadIdx.x == 0) *ctr = BuildCounters{};
+    }
+    long long mn = LLONG_MAX, mx = LLONG_MIN;
+    for (unsigned b = threadIdx.x; b < ntiles; b += blockDim.x) {
+        mn = min(mn, mm[kAnchorHdr + 2 * b]);
+        mx = max(mx, mm[kAnchorHdr + 2 * b + 1]);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        mn = min(mn, (long long)__shfl_xor(mn, d, 64));
+        mx = max(mx, (long long)__shfl_xor(mx, d, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_mn[threadIdx.x >> 6] = mn;
+        s_mx[threadIdx.x >> 6] = mx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
+            mn = min(mn, s_mn[w]);
+            mx = max(mx, s_mx[w]);
+        }
+        const long long ablk = (long long)ld_key<K>(akeys, 0) >> kDenseBlockLog;
+        mm[0] = mn;
+        mm[1] = mx;
+        mm[2] = (mn >> kDenseBlockLog) - ablk + kAnchorBias;  // read only when the range takes the dense layout
+        *aflag = 0ull;
+        if (mbox != nullptr) {  // host mailbox (fine-grained): result, then the sequence number
+            mbox[0] = mn;
+            mbox[1] = mx;
+            __hip_atomic_store(&mbox[2], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
 // The build's key-range reduction: per-block partials, then minmax_final_kernel (result
 // and host mailbox). Two launches, but 256-thread blocks that fit beside the previous
 // step's probe kernels in the pipelined bench: the one-launch form (1024-thread blocks)
@@ -4099,9 +4280,10 @@ bool frag_build_ok(const ChunkGeom& g, int64_t ftiles) {
     return g.dense && dense_one_level(g.nchunks) && dense_blocks(g.nchunks) <= (uint32_t)kSlMaxSlices &&
            ftiles <= kFragMaxTiles;
 }
-int64_t frag_build_scratch_bytes(const ChunkGeom& g, int64_t ftiles, int64_t total) {
+int64_t frag_build_scratch_bytes(const ChunkGeom& g, int64_t ftiles, int64_t total, bool anchor) {
     const int64_t nbins = dense_blocks(g.nchunks) + 1;
-    return 2 * ftiles * kSlTile + 2 * ftiles * kSlTile + 2 * ftiles * nbins + 2 * ((ftiles + 63) & ~(int64_t)63) * nbins +
+    const int64_t tbins = anchor ? kSlHistBins : nbins;  // anchor build: the tiles' bounds of every anchor bin
+    return 2 * ftiles * kSlTile + 2 * ftiles * kSlTile + 2 * ftiles * tbins + 2 * ((ftiles + 63) & ~(int64_t)63) * nbins +
            16 * total + 6 * 256;  // spill pool: the spilled rows twice (gathered, then by sub-range)
 }
 
@@ -4126,9 +4308,13 @@ uint32_t frag_threads() {  // read per build, so that tests can run both forms i
 hipError_t launch_build_frag(int key_bytes, const Segment* h_segs, int nseg, const ChunkGeom& g, int64_t ftiles,
                              void* scratch, uint32_t* tile_base, const uint64_t* ids32, uint32_t* dense,
                              uint32_t* dup_rows, BigSeg* big, BuildCounters* ctr, const Segment* d_segs, int64_t total,
-                             bool ids_as_rows, int big_grid, const SpecGeo& spec, hipStream_t s) {
+                             bool ids_as_rows, int big_grid, const SpecGeo& spec, hipStream_t s, const AnchorArgs& aa,
+                             int64_t* mbox, int64_t seq, bool publish) {
     // spec.mm: the grid and the scratch cover g's `cap` blocks; the kernels take theirs from
-    // the key range in device memory (SpecGeo)
+    // the key range in device memory (SpecGeo). spec.anchor: that range comes from the
+    // partition itself (anchor_fold_kernel; mbox, seq: its host mailbox; publish: it stores
+    // the segments to d_segs and zeroes ctr).
+    const bool anchor = spec.mm != nullptr && spec.anchor != 0;
     const uint32_t nblk = dense_blocks(g.nchunks), nbins = nblk + 1;
     constexpr uint32_t GV = kDenseSub << kDenseBlockShift;
     const uint32_t wlog = 31 - __builtin_clz(GV);
@@ -4136,7 +4322,7 @@ hipError_t launch_build_frag(int key_bytes, const Segment* h_segs, int nseg, con
     uintptr_t p = a256((uintptr_t)scratch);
     uint16_t* ko = (uint16_t*)p;   p = a256(p + 2 * ftiles * kSlTile);
     uint16_t* rl = (uint16_t*)p;   p = a256(p + 2 * ftiles * kSlTile);
-    uint16_t* toff = (uint16_t*)p; p = a256(p + 2 * ftiles * nbins);
+    uint16_t* toff = (uint16_t*)p; p = a256(p + 2 * ftiles * (anchor ? (uint32_t)kSlHistBins : nbins));
     uint16_t* toffT = (uint16_t*)p; p = a256(p + 2 * ((ftiles + 63) & ~(int64_t)63) * nbins);
     // Measured (r04) and not kept: the partition writing the bounds in the 64-tile layout
     // itself (no transpose launch): its scattered 2-byte stores cost the partition what the
@@ -4157,13 +4343,39 @@ hipError_t launch_build_frag(int key_bytes, const Segment* h_segs, int nseg, con
                                                                    sg.voff, sg.n, vec, ko, rl, toff, 0, t0,          \
                                                                    sg.row_base, tile_base, nullptr, nullptr, nullptr, \
                                                                    nullptr, spec)
-        if (key_bytes == 8) {
+#define DFP_BLPA(KT, HV)                                                                                        \
+    sl_partition_kernel<KT, HV, kSlTileLog, true><<<(unsigned)nt, kSlThreads, 0, s>>>(                          \
+        0, 0, wlog, 0, sg.keys, sg.valid, sg.voff, sg.n, vec, ko, rl, toff, 0, t0, sg.row_base, tile_base, aa.flag, \
+        reinterpret_cast<unsigned long long*>(aa.part), (uint32_t*)const_cast<void*>(aa.keys), nullptr, spec)
+        if (anchor) {
+            if (key_bytes == 8) {
+                if (sg.valid) DFP_BLPA(int64_t, true); else DFP_BLPA(int64_t, false);
+            } else {
+                if (sg.valid) DFP_BLPA(int32_t, true); else DFP_BLPA(int32_t, false);
+            }
+        } else if (key_bytes == 8) {
             if (sg.valid) DFP_BLP(int64_t, true); else DFP_BLP(int64_t, false);
         } else {
             if (sg.valid) DFP_BLP(int32_t, true); else DFP_BLP(int32_t, false);
         }
 #undef DFP_BLP
+#undef DFP_BLPA
         t0 += nt;
+    }
+    if (anchor) {
+        SegArgs sa{};
+        if (publish) {
+            if (nseg > kArgSegs) return hipErrorInvalidValue;
+            for (int i = 0; i < nseg; ++i) sa.s[i] = h_segs[i];
+        }
+        if (key_bytes == 8)
+            anchor_fold_kernel<int64_t><<<1, 1024, 0, s>>>(aa.part, (unsigned)ftiles, aa.keys, aa.flag,
+                                                           (long long*)mbox, (long long)seq,
+                                                           const_cast<Segment*>(d_segs), sa, nseg, publish ? ctr : nullptr);
+        else
+            anchor_fold_kernel<int32_t><<<1, 1024, 0, s>>>(aa.part, (unsigned)ftiles, aa.keys, aa.flag,
+                                                           (long long*)mbox, (long long)seq,
+                                                           const_cast<Segment*>(d_segs), sa, nseg, publish ? ctr : nullptr);
     }
     sl_toff_transpose_kernel<<<(unsigned)((ftiles + 63) / 64 * ((nblk + kSlTrChunk) / kSlTrChunk)), 256, 0, s>>>(
         toff, nbins, ftiles, toffT, spec);

@@ -46,11 +46,13 @@ int64_t frag_build_tiles(const int64_t* seg_n, int nseg, int tile_log = 14);
 // tile log of the hashed frag build's tiles (15 by default, DFP_HJ_HB_TILE_LOG=14)
 int hashed_build_tile_log();
 bool frag_build_ok(const ChunkGeom& g, int64_t ftiles);
-int64_t frag_build_scratch_bytes(const ChunkGeom& g, int64_t ftiles, int64_t total);
+int64_t frag_build_scratch_bytes(const ChunkGeom& g, int64_t ftiles, int64_t total, bool anchor = false);
 hipError_t launch_build_frag(int key_bytes, const Segment* h_segs, int nseg, const ChunkGeom& g, int64_t ftiles,
                              void* scratch, uint32_t* tile_base, const uint64_t* ids32, uint32_t* dense,
                              uint32_t* dup_rows, BigSeg* big, BuildCounters* ctr, const Segment* d_segs, int64_t total,
-                             bool ids_as_rows, int big_grid, const SpecGeo& spec, hipStream_t s);
+                             bool ids_as_rows, int big_grid, const SpecGeo& spec, hipStream_t s,
+                             const AnchorArgs& aa = AnchorArgs{}, int64_t* mbox = nullptr, int64_t seq = 0,
+                             bool publish = false);
 // Hashed builds of chunks <= 1024 buckets and <= kFragMaxTiles tiles: the probe's hashed
 // partition on the build keys (1024-bucket slices, passes of <= 2047 slices), then one
 // workgroup per slice gathers its rows from the tiles' fragments and builds the slice's

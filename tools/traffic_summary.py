@@ -24,7 +24,7 @@ PROBE_KERNELS = ("probe_fused_kernel", "probe_lookup_kernel", "probe_emit_kernel
                  "pp_count_kernel", "sl_partition_kernel", "hs_partition_kernel", "hs_partition32_kernel", "sl_toff_transpose_kernel",
                  "sl_lookup_kernel",
                  "sl_count_kernel", "sl_emit_kernel")
-BUILD_KERNELS = ("key_minmax_kernel", "key_minmax_part_kernel", "minmax_final_kernel", "coarse_hist_kernel", "coarse_scatter", "fine_hist_kernel",
+BUILD_KERNELS = ("key_minmax_kernel", "key_minmax_part_kernel", "minmax_final_kernel", "anchor_fold_kernel", "coarse_hist_kernel", "coarse_scatter", "fine_hist_kernel",
                  "fine_scatter", "chunk_starts_kernel", "scan_reduce_kernel<unsigned int>",
                  "scan_down_kernel<unsigned int>", "chunk_build_kernel", "dup_sort_big_kernel", "sl_partition_kernel",
                  "sl_toff_transpose_kernel", "dense_frag_build_kernel", "hs_partition_kernel", "hs_partition32_kernel",
