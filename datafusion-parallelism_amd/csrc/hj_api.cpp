@@ -2062,6 +2062,77 @@ hj_status hj_probe_match(const hj_table* t, const void* keys, const uint8_t* val
     return note_probe(t, s);  // hj_table_free waits for it
 }
 
+// ---- pair plan and pair window --------------------------------------------------------
+
+namespace {
+const char* const kPlanMulti = "the pair plan is not defined for a multi-GPU table (probe its pairs instead)";
+// after the argument checks: a null table is HJ_ERR_NO_DEVICE where no GPU is visible (a
+// table cannot exist there, so only a null one asks the runtime), else as every probe
+hj_status check_plan_table(const hj_table* t) {
+    if (t == nullptr && device_count() == 0) return fail(HJ_ERR_NO_DEVICE, "no GPU visible");
+    hj_status st = check_table(t);
+    if (st != HJ_OK) return st;
+    if (t->multi) return fail(HJ_ERR_INVALID, kPlanMulti);
+    return HJ_OK;
+}
+}  // namespace
+
+int64_t hj_pair_plan_bytes(const hj_table* t, int64_t n) {
+    if (check_table(t) != HJ_OK) return -1;
+    if (t->multi) {
+        (void)fail(HJ_ERR_INVALID, kPlanMulti);
+        return -1;
+    }
+    if (check_probe_args(n, 0, 0, nullptr) != HJ_OK) return -1;
+    return pair_plan_layout(n).bytes;
+}
+
+hj_status hj_pair_plan(const hj_table* t, const void* keys, const uint8_t* validity, int64_t validity_offset,
+                       int64_t n, void* plan, int64_t* d_total, void* stream) {
+    // arguments first, before any device call
+    if (plan == nullptr) return fail(HJ_ERR_INVALID, "null plan");
+    if ((reinterpret_cast<uintptr_t>(plan) & 7) || (reinterpret_cast<uintptr_t>(d_total) & 7))
+        return fail(HJ_ERR_INVALID, "plan and d_total must be 8-byte aligned");
+    hj_status st = check_probe_args(n, 0, 0, nullptr);
+    if (st != HJ_OK) return st;
+    if (n > 0 && keys == nullptr) return fail(HJ_ERR_INVALID, "null keys");
+    if ((st = check_plan_table(t)) != HJ_OK) return st;
+    HIP_TRY(hipSetDevice(t->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((st = wait_built(t, s)) != HJ_OK) return st;  // the lookup orders itself after the build
+    const PlanLayout L = pair_plan_layout(n);
+    char* p = static_cast<char*>(plan);
+    HIP_TRY(launch_pair_plan_lookup(t->key_bytes, view_of(t), keys, validity, validity_offset, n,
+                                    reinterpret_cast<uint32_t*>(p + L.refs), reinterpret_cast<uint32_t*>(p + L.counts),
+                                    reinterpret_cast<unsigned long long*>(p + L.blocks), s));
+    HIP_TRY(launch_pair_plan_finish(plan, n, d_total, s));
+    return note_probe(t, s);  // hj_table_free waits for it
+}
+
+hj_status hj_pair_window(const hj_table* t, const void* plan, int64_t n, const uint32_t* probe_ids,
+                         uint32_t probe_base, int64_t pair_lo, int64_t capacity, uint64_t* out_build,
+                         uint32_t* out_probe, int64_t* d_written, void* stream) {
+    if (plan == nullptr) return fail(HJ_ERR_INVALID, "null plan");
+    if ((reinterpret_cast<uintptr_t>(plan) & 7) || (reinterpret_cast<uintptr_t>(d_written) & 7) ||
+        (reinterpret_cast<uintptr_t>(out_build) & 7) || (reinterpret_cast<uintptr_t>(out_probe) & 3))
+        return fail(HJ_ERR_INVALID, "plan, d_written and out_build must be 8-byte, out_probe 4-byte aligned");
+    if (pair_lo < 0) return fail(HJ_ERR_INVALID, "negative pair_lo");
+    hj_status st = check_probe_args(n, probe_base, capacity, nullptr);
+    if (st != HJ_OK) return st;
+    if (capacity > 0 && (out_build == nullptr || out_probe == nullptr))
+        return fail(HJ_ERR_INVALID, "null output with capacity > 0");
+    if (capacity > (int64_t)0x7FFFFFFF * kWinTile) return fail(HJ_ERR_INVALID, "capacity exceeds 2^42 pairs");
+    if (probe_ids != nullptr && probe_base != 0)
+        return fail(HJ_ERR_INVALID, "probe_ids and probe_base are exclusive: add the base to the ids");
+    if ((st = check_plan_table(t)) != HJ_OK) return st;
+    HIP_TRY(hipSetDevice(t->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((st = wait_built(t, s)) != HJ_OK) return st;  // the window reads the duplicate segments and the ids
+    HIP_TRY(launch_pair_window(view_of(t), plan, n, probe_ids, probe_base, pair_lo, capacity, out_build, out_probe,
+                               d_written, s));
+    return note_probe(t, s);
+}
+
 hj_status hj_probe(const hj_table* t, const void* keys, const uint8_t* validity, int64_t validity_offset, int64_t n,
                    uint32_t flags, void* stream, hj_pairs* out) {
     hj_status st = check_table(t);

@@ -5209,6 +5209,77 @@ hipError_t launch_probe_match(int key_bytes, const TableView& tv, const void* ke
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// pair plan, pass 1: the match probe's lookup, kept per row. Every row's ref and resolved
+// pair count go to the plan's scratch, and every block of kPlanBlockRows rows leaves its
+// (matched rows, pairs) totals; the scan of those totals and the compaction are launches
+// of their own (hj_window.hip), so no workgroup waits for another. Where the reference's
+// get_matching_indices (src/shared/shared.rs:29-47) emits a probe batch's pairs in one
+// piece, the plan keeps "how many pairs, and where" and the windows emit them in slices.
+// ---------------------------------------------------------------------------
+static_assert(kPlanBlockRows == kMatchRows, "a plan block is one iteration of the match probe's workgroup");
+
+template <typename K, bool HAS_VALID>
+__global__ void __launch_bounds__(kMatchThreads)
+pair_plan_lookup_kernel(TableView tv, const void* __restrict__ keys, const uint8_t* __restrict__ valid, int64_t voff,
+                        int64_t n, bool vec, uint32_t* __restrict__ refs, uint32_t* __restrict__ counts, bool svec,
+                        unsigned long long* __restrict__ btot) {
+    __shared__ unsigned long long s_m[kMatchThreads / 64], s_p[kMatchThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t blk = blockIdx.x; blk * kMatchRows < n; blk += gridDim.x) {
+        const int64_t row0 = blk * kMatchRows + (int64_t)threadIdx.x * 4;
+        uint32_t ref[4] = {kMiss, kMiss, kMiss, kMiss}, cnt[4] = {0, 0, 0, 0};
+        if (row0 < n) lookup4<K, HAS_VALID>(tv, keys, valid, voff, n, vec, row0, ref, cnt);
+        unsigned long long matched = 0, pairs = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            cnt[q] = resolve_count(tv.dup_rows, ref[q], cnt[q], tv.off_mask);
+            matched += cnt[q] != 0;
+            pairs += cnt[q];
+        }
+        if (svec && row0 + 4 <= n) {
+            *reinterpret_cast<uint4*>(refs + row0) = make_uint4(ref[0], ref[1], ref[2], ref[3]);
+            *reinterpret_cast<uint4*>(counts + row0) = make_uint4(cnt[0], cnt[1], cnt[2], cnt[3]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (row0 + q < n) {
+                    refs[row0 + q] = ref[q];
+                    counts[row0 + q] = cnt[q];
+                }
+        }
+        const unsigned long long wm = wave_sum<unsigned long long>(matched);
+        const unsigned long long wp = wave_sum<unsigned long long>(pairs);
+        if (lane == 0) { s_m[wave] = wm; s_p[wave] = wp; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long tm = 0, tp = 0;
+            for (int w = 0; w < kMatchThreads / 64; ++w) { tm += s_m[w]; tp += s_p[w]; }
+            btot[2 * blk] = tm;
+            btot[2 * blk + 1] = tp;
+        }
+        __syncthreads();
+    }
+}
+
+hipError_t launch_pair_plan_lookup(int key_bytes, const TableView& tv, const void* keys, const uint8_t* valid,
+                                   int64_t voff, int64_t n, uint32_t* refs, uint32_t* counts,
+                                   unsigned long long* btot, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15) == 0;
+    const bool svec = ((reinterpret_cast<uintptr_t>(refs) | reinterpret_cast<uintptr_t>(counts)) & 15) == 0;
+    const unsigned grid = (unsigned)std::min<int64_t>((n + kMatchRows - 1) / kMatchRows, kMatchMaxBlocks);
+#define DFP_PLAN(KT, HV) \
+    pair_plan_lookup_kernel<KT, HV><<<grid, kMatchThreads, 0, s>>>(tv, keys, valid, voff, n, vec, refs, counts, svec, btot)
+    if (key_bytes == 8) {
+        if (valid) DFP_PLAN(int64_t, true); else DFP_PLAN(int64_t, false);
+    } else {
+        if (valid) DFP_PLAN(int32_t, true); else DFP_PLAN(int32_t, false);
+    }
+#undef DFP_PLAN
+    return hipGetLastError();
+}
+
 // A gathered direct-addressed table (the sharded-build broadcast plan): each piece's
 // duplicated-key refs point into its own segment array; once the pieces' segment arrays
 // sit one after another, the refs of one piece move by that piece's base. Streams the

@@ -117,6 +117,37 @@ hipError_t launch_probe_match(int key_bytes, const TableView& tv, const void* ke
                               int64_t n, uint8_t* out_bitmap, uint32_t* out_counts, uint8_t* flags, int64_t nflags,
                               int64_t* d_stats, void* workspace, uint64_t claim_bits, hipStream_t s);
 
+// ---- pair plan and pair window (hj_kernels.hip: the lookup; hj_window.hip: the rest) ----
+// The plan of a probe call's n rows, in caller memory of pair_plan_bytes(n) bytes (8-byte
+// aligned; every section starts at a multiple of 16 bytes from its base):
+//   header   u64 m = matched rows, u64 total = pairs (64 bytes reserved)
+//   offsets  u64[n + 1]: offsets[e] = pairs before matched row e, offsets[m] = total
+//   entries  (u32 row, u32 ref)[n]: the matched rows in row order
+//   scratch  u32 refs[n], u32 counts[n] (every row, from the lookup), u64[2 * blocks] the
+//            (matched, pairs) totals of the blocks of kPlanBlockRows rows, scanned in place
+// Only header, offsets[0..m] and entries[0..m) are read by the windows.
+constexpr int64_t kPlanHeaderBytes = 64;
+constexpr int kPlanBlockRows = 1024;
+struct PlanLayout {
+    int64_t offsets, entries, refs, counts, blocks, bytes;  // byte offsets of the sections; total size
+    int64_t nblocks;
+};
+PlanLayout pair_plan_layout(int64_t n);
+// pass 1 (hj_kernels.hip): refs[i], counts[i] of every row i < n, and per block of
+// kPlanBlockRows rows btot[2 * b] = matched rows, btot[2 * b + 1] = pairs. n > 0.
+hipError_t launch_pair_plan_lookup(int key_bytes, const TableView& tv, const void* keys, const uint8_t* valid,
+                                   int64_t voff, int64_t n, uint32_t* refs, uint32_t* counts,
+                                   unsigned long long* btot, hipStream_t s);
+// passes 2 and 3 (hj_window.hip): scan of the block totals (its own launch, one workgroup),
+// then per block the compaction of its matched rows; *d_total (optional) = pairs. n >= 0.
+hipError_t launch_pair_plan_finish(void* plan, int64_t n, int64_t* d_total, hipStream_t s);
+// pairs [pair_lo, pair_lo + capacity) of the plan's canonical order -> out_b / out_p from
+// index 0; *d_written (optional) = pairs written. The grid follows `capacity` alone.
+constexpr int kWinTile = 2048;  // output pairs of one workgroup
+hipError_t launch_pair_window(const TableView& tv, const void* plan, int64_t n, const uint32_t* probe_ids,
+                              uint32_t probe_base, int64_t pair_lo, int64_t capacity, uint64_t* out_b,
+                              uint32_t* out_p, int64_t* d_written, hipStream_t s);
+
 // ---- table queries -------------------------------------------------------
 // refs[v] of a duplicated key (bit 31, not kMiss): offset field (mask) + base, v < n
 hipError_t launch_dense_rebase(uint32_t* refs, uint64_t n, uint32_t base, uint32_t mask, hipStream_t s);

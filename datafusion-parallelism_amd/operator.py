@@ -199,6 +199,34 @@ class GpuIndexLookup:
         kidx = [e if isinstance(e, int) else rb.schema.get_field_index(e) for e in sh.key_exprs]
         return filter_equal_pairs([bcols[i] for i in kidx], pcols, b, p)
 
+    def matching_windows(self, probe_keys: Sequence[DeviceColumn], max_pairs: int,
+                         build_side_records: pa.RecordBatch | None = None):
+        """matching_indices_device in slices: an iterator over the same pairs, in the same
+        order, as consecutive windows of at most max_pairs candidate pairs (HashTable.pair_plan:
+        one lookup, then one window at a time), each after the equality re-check of a
+        composite key. No pair buffer exceeds max_pairs elements."""
+        pcols = list(probe_keys)
+        sh = self._shared
+        composite = sh is not None and (sh.composite or not _is_simple_key(pcols))
+        if not composite and not _is_simple_key(pcols):
+            raise HjError(HJ_ERR_INVALID, "probe keys do not match the build keys (one Int32/Int64 column)")
+        if composite and len(pcols) != len(sh.key_exprs):
+            raise HjError(HJ_ERR_INVALID, f"{len(pcols)} probe key columns for {len(sh.key_exprs)} build key columns")
+        if pcols[0].length == 0:
+            return
+        if composite:
+            keys, valid = composite_keys(pcols)
+            plan = self.table.pair_plan(keys, valid, prefilter=self._prefilter())
+            rb = build_side_records if build_side_records is not None else sh.concatenated()
+            bcols = self.build_columns(rb)
+            kcols = [bcols[e if isinstance(e, int) else rb.schema.get_field_index(e)] for e in sh.key_exprs]
+            for b, p in plan.windows(max_pairs):
+                yield filter_equal_pairs(kcols, pcols, b, p)
+        else:
+            k = pcols[0]
+            plan = self.table.pair_plan(k.key_tensor(), k.valid, valid_offset=k.voff, prefilter=self._prefilter())
+            yield from plan.windows(max_pairs)
+
     def matching_indices(self, probe_keys: pa.Array) -> tuple[pa.UInt64Array, pa.UInt32Array]:
         """Host form of matching_indices_device (UInt64 build, UInt32 probe)."""
         b, p = self.table.probe(probe_keys)
@@ -216,8 +244,9 @@ class _SharedBuild:
     """State shared by all partitions of one build (JoinStateInstances)."""
 
     def __init__(self, parallelism: int, device: int, devices: Sequence[int] | None = None, plan: str = "auto",
-                 prefilter: bool = False, match_probe: bool = False):
+                 prefilter: bool = False, match_probe: bool = False, max_output_rows: int | None = None):
         self.parallelism = parallelism
+        self.max_output_rows = max_output_rows  # probe batches emit in windows of at most this many rows
         self.prefilter = prefilter      # probes go through a key filter over the build keys
         self.match_probe = match_probe  # semi / anti joins probe for matches, not pairs (probe_batch)
         self._filter: KeyFilter | None = None
@@ -308,8 +337,20 @@ class BuildImplementation:
 
     def __init__(self, build_implementation_version: JoinReplacement, parallelism: int,
                  input_schema: pa.Schema | None = None, device: int = 0, devices: Sequence[int] | None = None,
-                 plan: str = "auto", prefilter: bool = False, match_probe: bool = False):
-        """prefilter: every probe first drops the rows a key filter over the build keys
+                 plan: str = "auto", prefilter: bool = False, match_probe: bool = False,
+                 max_output_rows: int | None = None):
+        """max_output_rows: None (default) changes nothing. An integer N >= 1 bounds the memory
+        of every probe batch by N instead of by the join's fan-out: the batch's pairs are
+        planned once (HashTable.pair_plan) and taken window by window, each of at most N
+        candidate pairs, which pass the equality re-check and the JoinFilter, are marked and
+        gathered before the next window is written, so no pair buffer and no gathered column
+        exceeds N rows. probe_batch then returns a list of RecordBatches of at most N rows
+        each - the same rows in the same order as without the bound - and
+        finalize_build_side emits in chunks of at most N as well. Not with `devices=` (a
+        multi-GPU table has no pair plan): HjError(HJ_ERR_INVALID) here, since a memory
+        bound that is silently ignored is worse than an error. match_probe=True keeps its
+        path for the joins it takes; its selected rows are chunked.
+        prefilter: every probe first drops the rows a key filter over the build keys
         rejects (KeyFilter; same output for every join type: the filter only removes rows
         that have no pair).
         match_probe: LeftSemi, LeftAnti, RightSemi and RightAnti probe batches ask the table
@@ -334,8 +375,14 @@ class BuildImplementation:
                 "implements JoinReplacement.Gpu")
         if devices is not None and len(devices) < 1:
             raise HjError(HJ_ERR_INVALID, "devices must name at least one GPU")
+        if max_output_rows is not None:
+            if isinstance(max_output_rows, bool) or not isinstance(max_output_rows, int) or max_output_rows < 1:
+                raise HjError(HJ_ERR_INVALID, "max_output_rows must be None or an integer >= 1")
+            if devices is not None:
+                raise HjError(HJ_ERR_INVALID, "max_output_rows is not available on a multi-GPU table (devices=): "
+                                              "the pair plan is defined for one-device tables")
         self.parallelism = parallelism
-        self._shared = _SharedBuild(parallelism, device, devices, plan, prefilter, match_probe)
+        self._shared = _SharedBuild(parallelism, device, devices, plan, prefilter, match_probe, max_output_rows)
         self._shared.schema = input_schema
 
     def build_side(self, partition: int, stream: Iterable[pa.RecordBatch], build_expressions: Sequence[str | int],
@@ -417,11 +464,13 @@ def _takes_match_path(jt: JoinType, filter, lookup: GpuIndexLookup, key_cols: Se
 
 def probe_batch(join_type: JoinType, probe_expressions: Sequence[str | int], build_expressions: Sequence[str | int],
                 filter: JoinFilter | None, build_side_records: pa.RecordBatch, read_only_join_map: GpuIndexLookup,
-                probe_batch: pa.RecordBatch, build_visited: torch.Tensor | None = None) -> pa.RecordBatch | None:
+                probe_batch: pa.RecordBatch, build_visited: torch.Tensor | None = None
+                ) -> pa.RecordBatch | list[pa.RecordBatch] | None:
     """One probe batch of any join type: the lookup_*_probe_batch functions of
     src/operator/probe_lookup_implementation/{inner,left_outer,right_outer,full,left_semi,
     left_anti,right_semi,right_anti}.rs. Build-side join types only mark `build_visited`
-    here (their rows are emitted by finalize_build_side)."""
+    here (their rows are emitted by finalize_build_side). Under max_output_rows
+    (BuildImplementation) the result is a list of RecordBatches of at most that many rows."""
     jt = JoinType.parse(join_type)
     lookup = read_only_join_map
     dev = lookup.device
@@ -430,6 +479,10 @@ def probe_batch(join_type: JoinType, probe_expressions: Sequence[str | int], bui
     probe_cols = [DeviceColumn.from_arrow(c, dev) for c in probe_batch.columns]
     key_cols = [probe_cols[e if isinstance(e, int) else probe_batch.schema.get_field_index(e)]
                 for e in probe_expressions]
+    limit = lookup._shared.max_output_rows if lookup._shared is not None else None
+    if limit is not None:
+        return _probe_batch_windowed(jt, filter, build_side_records, lookup, probe_batch, probe_cols, key_cols,
+                                     build_visited, limit)
     if _takes_match_path(jt, filter, lookup, key_cols, n):
         # no pairs: the matched-probe bitmap (get_semi_indices / get_anti_indices) and the
         # visited build rows (set_ones) straight from the lookup
@@ -462,32 +515,108 @@ def probe_batch(join_type: JoinType, probe_expressions: Sequence[str | int], bui
     return _batch([c.take(b) for c in build_cols] + [c.take(p) for c in probe_cols], bnames + pnames)
 
 
+def _row_chunks(rows: torch.Tensor, limit: int) -> list[torch.Tensor]:
+    """`rows` in consecutive pieces of at most `limit` (one empty piece for no rows: the
+    unbounded path emits an empty batch there too)."""
+    return [rows[lo:lo + limit] for lo in range(0, rows.numel(), limit)] or [rows]
+
+
+def _probe_batch_windowed(jt: JoinType, filter: JoinFilter | None, build_side_records: pa.RecordBatch,
+                          lookup: GpuIndexLookup, probe_batch: pa.RecordBatch, probe_cols: list[DeviceColumn],
+                          key_cols: list[DeviceColumn], build_visited: torch.Tensor | None,
+                          limit: int) -> list[pa.RecordBatch]:
+    """probe_batch under max_output_rows: the same rows in the same order as the unbounded
+    path, as RecordBatches of at most `limit` rows. The pairs come window by window
+    (GpuIndexLookup.matching_windows); each window is re-checked, filtered, marked and
+    gathered before the next one exists. The flags of both sides accumulate over the
+    windows; the once-per-batch rows (unmatched probe rows of Right / Full, the selected
+    rows of RightSemi / RightAnti) follow the last window in chunks."""
+    dev = lookup.device
+    n = probe_batch.num_rows
+    pnames = list(probe_batch.schema.names)
+    if _takes_match_path(jt, filter, lookup, key_cols, n):
+        k = key_cols[0]
+        left = jt in (JoinType.LeftSemi, JoinType.LeftAnti)
+        m = lookup.table.probe_match(k.key_tensor(), k.valid, valid_offset=k.voff,
+                                     build_flags=build_visited if left else None)
+        if left:
+            return []
+        rows = select_bitmap(m.bitmap, n, 1 if jt is JoinType.RightSemi else 0)
+        return [_batch([c.take(r) for c in probe_cols], pnames) for r in _row_chunks(rows, limit)]
+    build_cols = lookup.build_columns(build_side_records)
+    bnames = list(build_side_records.schema.names)
+    emits_pairs = jt in (JoinType.Inner, JoinType.Left, JoinType.Right, JoinType.Full)
+    probe_side = jt in (JoinType.Right, JoinType.Full, JoinType.RightSemi, JoinType.RightAnti)
+    probe_flags = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev) if probe_side else None
+    out = []
+    for b, p in lookup.matching_windows(key_cols, limit, build_side_records):
+        if filter is not None:
+            b, p = _apply_filter(filter, build_cols, bnames, probe_cols, pnames, b, p)
+        if b.numel() == 0:
+            continue
+        if jt.marks_build and build_visited is not None:
+            mark_rows(b, build_side_records.num_rows, build_visited)
+        if probe_side:
+            mark_rows(p, n, probe_flags)
+        if emits_pairs:
+            out.append(_batch([c.take(b) for c in build_cols] + [c.take(p) for c in probe_cols], bnames + pnames))
+    if jt in (JoinType.LeftSemi, JoinType.LeftAnti):
+        return []
+    if jt in (JoinType.RightSemi, JoinType.RightAnti):
+        rows = select_rows(probe_flags, 1 if jt is JoinType.RightSemi else 0, n).to(torch.int32)
+        return [_batch([c.take(r) for c in probe_cols], pnames) for r in _row_chunks(rows, limit)]
+    if jt in (JoinType.Right, JoinType.Full):
+        # append_right_indices(preserve_order = false): unmatched probe rows after the pairs
+        unmatched = select_rows(probe_flags, 0, n).to(torch.int32)
+        for r in _row_chunks(unmatched, limit) if unmatched.numel() else []:
+            nulls = torch.full((r.numel(),), -1, dtype=torch.int64, device=dev)
+            out.append(_batch([c.take(nulls) for c in build_cols] + [c.take(r) for c in probe_cols], bnames + pnames))
+    if not out:  # no row at all: the empty batch the unbounded path returns
+        e_b = torch.empty(0, dtype=torch.int64, device=dev)
+        e_p = torch.empty(0, dtype=torch.int32, device=dev)
+        out.append(_batch([c.take(e_b) for c in build_cols] + [c.take(e_p) for c in probe_cols], bnames + pnames))
+    return out
+
+
 def finalize_build_side(join_type: JoinType, build_side_records: pa.RecordBatch, lookup: GpuIndexLookup,
-                        build_visited: torch.Tensor, probe_schema: pa.Schema) -> pa.RecordBatch | None:
+                        build_visited: torch.Tensor, probe_schema: pa.Schema
+                        ) -> pa.RecordBatch | list[pa.RecordBatch] | None:
     """The once-only build-side emission of the last finishing partition
     (emit_matched_build_records / emit_unmatched_build_records, e.g.
-    left_semi.rs:166-178, left_outer.rs:174-193, full.rs:181-200)."""
+    left_semi.rs:166-178, left_outer.rs:174-193, full.rs:181-200). Under max_output_rows: a
+    list of RecordBatches of at most that many rows each."""
     jt = JoinType.parse(join_type)
     if not jt.marks_build:
         return None
     nb = build_side_records.num_rows
     rows = select_rows(build_visited, 1 if jt is JoinType.LeftSemi else 0, nb)
     cols = lookup.build_columns(build_side_records)
-    out = [c.take(rows).to_arrow() for c in cols]
-    names = list(build_side_records.schema.names)
-    if jt in (JoinType.Left, JoinType.Full):
-        out += [pa.nulls(rows.numel(), type=f.type) for f in probe_schema]
-        names += list(probe_schema.names)
-    return pa.RecordBatch.from_arrays(out, names=names)
+    limit = lookup._shared.max_output_rows if lookup._shared is not None else None
+
+    def emit(r: torch.Tensor) -> pa.RecordBatch:
+        out = [c.take(r).to_arrow() for c in cols]
+        names = list(build_side_records.schema.names)
+        if jt in (JoinType.Left, JoinType.Full):
+            out += [pa.nulls(r.numel(), type=f.type) for f in probe_schema]
+            names += list(probe_schema.names)
+        return pa.RecordBatch.from_arrays(out, names=names)
+
+    if limit is not None:
+        return [emit(r) for r in _row_chunks(rows, limit)]
+    return emit(rows)
 
 
 def lookup_inner_join_probe_batch(probe_expressions: Sequence[str | int], build_expressions: Sequence[str | int],
                                   filter, build_side_records: pa.RecordBatch, read_only_join_map: GpuIndexLookup,
                                   probe_batch: pa.RecordBatch, output_schema: pa.Schema | None = None
-                                  ) -> pa.RecordBatch:
-    """src/operator/probe_lookup_implementation/inner.rs:79-129."""
+                                  ) -> pa.RecordBatch | list[pa.RecordBatch]:
+    """src/operator/probe_lookup_implementation/inner.rs:79-129 (a list of RecordBatches
+    under max_output_rows)."""
     rb = globals()["probe_batch"](JoinType.Inner, probe_expressions, build_expressions, filter, build_side_records,
                                   read_only_join_map, probe_batch)
+    if isinstance(rb, list):
+        return [pa.RecordBatch.from_arrays(r.columns, schema=output_schema) if output_schema is not None else r
+                for r in rb]
     if output_schema is not None:
         return pa.RecordBatch.from_arrays(rb.columns, schema=output_schema)
     return rb
@@ -536,11 +665,15 @@ class _ProbeConsumer:
         for b in self.probe_stream:
             rb = probe_batch(jt, self.probe_expressions, self.build_expressions, self.filter, record_batch, lookup, b,
                              visited)
-            if rb is not None:
+            if isinstance(rb, list):  # max_output_rows: the batch's output in bounded pieces
+                out.extend(rb)
+            elif rb is not None:
                 out.append(rb)
         if jt.marks_build and self.finalizer.release():
             rb = finalize_build_side(jt, record_batch, lookup, visited, self.probe_schema)
-            if rb is not None:
+            if isinstance(rb, list):
+                out.extend(rb)
+            elif rb is not None:
                 out.append(rb)
         return out
 
@@ -556,8 +689,11 @@ class ParallelHashJoin:
                  on: Sequence[tuple[str, str]], join_type: JoinType | str = JoinType.Inner, device: int = 0,
                  replacement: JoinReplacement = JoinReplacement.Gpu, filter: JoinFilter | None = None,
                  right_schema: pa.Schema | None = None, devices: Sequence[int] | None = None, plan: str = "auto",
-                 prefilter: bool = False, match_probe: bool = False):
-        """devices / plan: one build table over several GPUs (BuildImplementation);
+                 prefilter: bool = False, match_probe: bool = False, max_output_rows: int | None = None):
+        """max_output_rows: None, or the most rows any output batch, pair buffer or gathered
+        column may have (BuildImplementation; same rows in the same order, in more batches;
+        not with `devices=`);
+        devices / plan: one build table over several GPUs (BuildImplementation);
         prefilter: probe through a key filter over the build keys (BuildImplementation);
         match_probe: semi and anti joins without a filter, on one Int32/Int64 key and one
         device, probe for matches instead of pairs (BuildImplementation; same output; the
@@ -573,7 +709,8 @@ class ParallelHashJoin:
         self.filter = filter
         self.right_schema = right_schema or next((b.schema for part in self.right for b in part), None)
         self._build = BuildImplementation(replacement, n, device=device, devices=devices, plan=plan,
-                                          prefilter=prefilter, match_probe=match_probe)
+                                          prefilter=prefilter, match_probe=match_probe,
+                                          max_output_rows=max_output_rows)
         self._finalizer = _Finalizer(n)
 
     def execute(self, partition: int) -> list[pa.RecordBatch]:

@@ -140,6 +140,46 @@ class MatchResult:
         return self._read()[1]
 
 
+class PairPlan:
+    """Result of HashTable.pair_plan: the pairs of one probe call, to be had in windows of the
+    canonical order. `total` (the pair count, may exceed 2^32) is read lazily and is the only
+    host synchronisation; the windows are device work on torch's current stream."""
+
+    def __init__(self, table: "HashTable", n: int, plan: torch.Tensor, d_total: torch.Tensor,
+                 probe_ids: torch.Tensor | None, probe_base: int):
+        self._table, self.n, self._plan, self._d_total = table, n, plan, d_total
+        self._ids, self._base, self._total = probe_ids, probe_base, None
+
+    @property
+    def total(self) -> int:
+        if self._total is None:
+            self._total = int(self._d_total.item())
+        return self._total
+
+    def window(self, lo: int, cap: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """Pairs [lo, lo + cap) of the canonical order as device tensors (build int64, probe
+        int32) of exactly w = clamp(total - lo, 0, cap) elements."""
+        if lo < 0 or cap < 0:
+            raise ValueError("lo and cap must not be negative")
+        w = max(min(self.total - lo, cap), 0)
+        dev = self._plan.device
+        ob = torch.empty(w, dtype=torch.int64, device=dev)
+        op = torch.empty(w, dtype=torch.int32, device=dev)
+        if w:
+            self._table.pair_window_async(self._plan.data_ptr(), self.n, lo, w, ob.data_ptr(), op.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream,
+                                          probe_ids_ptr=None if self._ids is None else self._ids.data_ptr(),
+                                          probe_base=self._base)
+        return ob, op
+
+    def windows(self, max_pairs: int):
+        """Consecutive windows of at most max_pairs pairs that cover every pair once."""
+        if max_pairs < 1:
+            raise ValueError("max_pairs must be at least 1")
+        for lo in range(0, self.total, max_pairs):
+            yield self.window(lo, max_pairs)
+
+
 class HashTable:
     """One shared build table for `parallelism` partitions (hj_build_begin .. finish)."""
 
@@ -407,6 +447,69 @@ class HashTable:
                                0 if build_flags is None else build_flags.numel(), d_stats.data_ptr())
         # ws and the key tensors are released in stream order by torch's allocator
         return MatchResult(n, bitmap, cnt, d_stats)
+
+    # -- pair plan / pair window (hj_pair_plan, hj_pair_window): pairs in bounded slices ---
+    def pair_plan_bytes(self, n: int) -> int:
+        """hj_pair_plan_bytes (no device work)."""
+        v = self._L.hj_pair_plan_bytes(self._h, int(n))
+        if v < 0:
+            check(_lib.HJ_ERR_INVALID, self._L)
+        return v
+
+    def pair_plan_async(self, keys_ptr: int, n: int, plan_ptr: int, d_total_ptr: int | None = None, stream: int = 0,
+                        valid_ptr: int | None = None, voff: int = 0) -> None:
+        """hj_pair_plan on raw device pointers (no sync, no allocation)."""
+        check(self._L.hj_pair_plan(self._h, keys_ptr or None, valid_ptr, voff, n, plan_ptr, d_total_ptr,
+                                   stream or None), self._L)
+
+    def pair_window_async(self, plan_ptr: int, n: int, pair_lo: int, capacity: int, out_build_ptr: int | None,
+                          out_probe_ptr: int | None, stream: int = 0, d_written_ptr: int | None = None,
+                          probe_ids_ptr: int | None = None, probe_base: int = 0) -> None:
+        """hj_pair_window on raw device pointers (no sync, no allocation): pairs
+        [pair_lo, pair_lo + capacity) of the plan of n rows; probe_idx = row, probe_ids[row]
+        or probe_base + row (ids and a base together are refused, as in probe_async)."""
+        if probe_ids_ptr is not None and probe_base:
+            raise ValueError("probe_ids_ptr and probe_base are exclusive: add the base to the ids")
+        check(self._L.hj_pair_window(self._h, plan_ptr, n, probe_ids_ptr, probe_base, pair_lo, capacity,
+                                     out_build_ptr, out_probe_ptr, d_written_ptr, stream or None), self._L)
+
+    def pair_plan(self, keys: torch.Tensor, valid=None, valid_offset: int = 0, probe_ids: torch.Tensor | None = None,
+                  probe_base: int = 0, prefilter=None) -> "PairPlan":
+        """Look every probe row up once and return a PairPlan, whose windows give the pairs
+        probe(keys, valid, device_output=True) would return, in the same order, in slices of
+        a size the caller chooses: peak memory is the window's, not the join's fan-out. keys:
+        a device tensor; valid: bool mask or LSB bitmap from bit valid_offset (as_key_input);
+        probe_ids: an int32 device tensor (the bits of a uint32) of the rows' probe indices,
+        or probe_base + row, not both. prefilter: a KeyFilter filled from this table's build
+        keys; the rows it rejects are dropped before the plan (they have no pairs), the
+        windows name the surviving rows by their ids. Not for a multi-GPU table
+        (HJ_ERR_INVALID). No host synchronisation here: PairPlan.total reads the pair count
+        lazily. Plan and windows run on torch's current stream."""
+        if not (isinstance(keys, torch.Tensor) and keys.is_cuda):
+            raise TypeError("pair_plan takes a device tensor of keys")
+        if probe_ids is not None and probe_base:
+            raise ValueError("probe_ids and probe_base are exclusive: add the base to the ids")
+        if probe_ids is not None and not (probe_ids.is_cuda and probe_ids.dtype == torch.int32 and
+                                          probe_ids.is_contiguous() and probe_ids.numel() == keys.numel()):
+            raise TypeError("probe_ids must be a contiguous int32 device tensor, one per key")
+        ki = as_key_input(keys, valid, valid_offset)
+        if ki.n and ki.key_type != self.key_type:
+            raise TypeError("probe key type differs from the build key type")
+        dev = keys.device
+        if prefilter is not None:
+            if prefilter.device != (dev.index or 0):
+                raise ValueError("the prefilter lives on another device than the probe keys")
+            fkeys, fids = prefilter.select(keys, valid, valid_offset, probe_base=probe_base)
+            if probe_ids is not None:
+                fids = probe_ids[fids.to(torch.int64)]
+            ki = KeyInput(fkeys.data_ptr(), None, 0, fkeys.numel(), ki.flags, ki.key_type, (fkeys, fids))
+            probe_ids, probe_base = fids, 0
+        plan = torch.empty(self.pair_plan_bytes(ki.n), dtype=torch.uint8, device=dev)
+        d_total = torch.empty(1, dtype=torch.int64, device=dev)
+        self.pair_plan_async(ki.ptr, ki.n, plan.data_ptr(), d_total.data_ptr(),
+                             torch.cuda.current_stream(dev).cuda_stream, ki.valid_ptr, ki.voff)
+        # the key tensors are released in stream order by torch's allocator
+        return PairPlan(self, ki.n, plan, d_total, probe_ids, probe_base)
 
     # -- sharded-build broadcast plan (hj_table_dense_piece / hj_table_wrap_dense) -------
     def dense_piece(self) -> dict:

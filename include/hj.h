@@ -326,6 +326,59 @@ hj_status hj_probe_match(const hj_table* t, const void* keys, const uint8_t* val
                          uint32_t* out_counts, uint8_t* build_flags, int64_t nflags,
                          int64_t* d_stats, void* workspace, void* stream);
 
+/* Pair plan and pair window: the pairs of one probe call in slices of bounded size.
+ * Replaces get_matching_indices (src/shared/shared.rs:29-47); new: the reference emits a
+ * probe batch's pairs in one piece, so its peak memory follows the join's fan-out. Here a
+ * plan looks every row up once and keeps how many pairs each matched row has and where they
+ * start; a window then writes pairs [pair_lo, pair_lo + capacity) of the canonical order.
+ * Opt-in: nothing else in the library calls them. Device pointers, asynchronous on `stream`,
+ * no host synchronisation, no allocation.
+ *
+ * Let S be the pairs hj_probe_async (or _ids / _base with the same probe_ids / probe_base)
+ * would produce for the same table, keys, validity and n at unlimited capacity, in its
+ * canonical order (probe rows ascending, each row's build rows descending).
+ *
+ * hj_pair_plan (replaces get_matching_indices, src/shared/shared.rs:29-47; new: the
+ * reference emits a probe batch's pairs in one piece) looks every row up once and leaves in
+ * `plan` what the windows need; the layout is opaque. `plan`: caller-owned device memory,
+ * 8-byte aligned, hj_pair_plan_bytes(t, n) bytes; the call's scratch lives inside it.
+ * *d_total (optional device int64) = |S|, which may exceed 2^32. Once the call has run the
+ * plan is read-only; it stays valid until the table is freed and does not depend on the key
+ * and validity buffers, which the caller may release. Three launches (lookup, scan of the
+ * block totals, compaction); none waits on another workgroup.
+ *
+ * hj_pair_window (replaces get_matching_indices, src/shared/shared.rs:29-47; new: the
+ * reference emits a probe batch's pairs in one piece) writes S[pair_lo + i] to
+ * out_build[i] / out_probe[i] for 0 <= i < w, w = clamp(|S| - pair_lo, 0, capacity), and
+ * *d_written (optional device int64) = w. Nothing at or beyond index w is written;
+ * pair_lo >= |S| or capacity == 0 writes nothing and sets w = 0. probe_ids (u32[n], may be
+ * NULL: probe_idx = probe_base + row) as hj_probe_async_ids'; probe_ids together with a
+ * non-zero probe_base is HJ_ERR_INVALID. `n` is the plan's. A window's device work follows
+ * `capacity` and log(matched rows): not n, not the rows without a match, not pair_lo. Any
+ * number of windows of one plan may run concurrently on different streams; the caller
+ * orders them after the plan as for any buffer.
+ *
+ * hj_pair_plan_bytes (replaces get_matching_indices, src/shared/shared.rs:29-47; new: the
+ * reference emits a probe batch's pairs in one piece): the plan's size, no device work; -1
+ * for a table the calls reject or n outside [0, 2^32).
+ *
+ * Both calls order themselves after the build, and hj_table_free waits for them. Tables:
+ * every one-device table hj_probe_match accepts; a multi-GPU table returns HJ_ERR_INVALID.
+ * n in [0, 2^32); n == 0 is valid and still writes d_total / d_written. pair_lo >= 0,
+ * 0 <= capacity <= 2^42. A null or misaligned plan, a misaligned d_total, d_written,
+ * out_build (8 bytes) or out_probe (4 bytes), a null output with capacity > 0:
+ * HJ_ERR_INVALID, checked before any device call; a null table where no GPU is visible:
+ * HJ_ERR_NO_DEVICE. */
+int64_t hj_pair_plan_bytes(const hj_table* t, int64_t n);
+hj_status hj_pair_plan(const hj_table* t, const void* keys, const uint8_t* validity,
+                       int64_t validity_offset, int64_t n, void* plan, int64_t* d_total,
+                       void* stream);
+hj_status hj_pair_window(const hj_table* t, const void* plan, int64_t n,
+                         const uint32_t* probe_ids, uint32_t probe_base,
+                         int64_t pair_lo, int64_t capacity,
+                         uint64_t* out_build, uint32_t* out_probe, int64_t* d_written,
+                         void* stream);
+
 /* Probe strategy for later probes of this process: 0 auto (sliced for tables past the L2s
  * - more than 2^20 key values or 2^16 buckets, at most 4 passes of 2047 slices - with a
  * probe side at least as large as the key range / bucket count, else fused),
