@@ -69,6 +69,25 @@ class HjKeyFilterInfo(ctypes.Structure):
                 ("dropped_adds", ctypes.c_int64)]
 
 
+HJ_CMP_EQ, HJ_CMP_NE, HJ_CMP_LT, HJ_CMP_LE, HJ_CMP_GT, HJ_CMP_GE = range(6)
+HJ_VAL_INT, HJ_VAL_UINT, HJ_VAL_FLOAT, HJ_VAL_BYTES = range(4)
+HJ_SIDE_BUILD, HJ_SIDE_PROBE, HJ_SIDE_CONST = range(3)
+
+
+class HjPairTerm(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_int), ("value_class", ctypes.c_int), ("lhs_side", ctypes.c_int),
+                ("lhs_col", ctypes.c_int), ("rhs_side", ctypes.c_int), ("rhs_col", ctypes.c_int),
+                ("rhs_const", ctypes.c_int64)]
+
+
+class HjPairPredicate(ctypes.Structure):
+    _fields_ = [("nterms", ctypes.c_int), ("terms", ctypes.POINTER(HjPairTerm)),
+                ("nbuild_cols", ctypes.c_int), ("build_cols", ctypes.POINTER(HjKeyColumn)),
+                ("build_rows", ctypes.c_int64),
+                ("nprobe_cols", ctypes.c_int), ("probe_cols", ctypes.POINTER(HjKeyColumn)),
+                ("probe_rows", ctypes.c_int64)]
+
+
 HJ_COMM_ID_BYTES = 128
 
 
@@ -143,6 +162,10 @@ SIGNATURES = [
     ("hj_equal_pairs_workspace_bytes", I64, [I64]),
     ("hj_filter_equal_pairs", I32, [I32, ctypes.POINTER(HjKeyColumn), ctypes.POINTER(HjKeyColumn), P, P, I64, P, P,
                                     P, P, P]),
+    ("hj_pair_predicate_check", I32, [ctypes.POINTER(HjPairPredicate)]),
+    ("hj_pair_filter_test", I32, [ctypes.POINTER(HjPairPredicate), P, P, I64, P, P, P]),
+    ("hj_pair_filter_workspace_bytes", I64, [I64]),
+    ("hj_pair_filter_select", I32, [ctypes.POINTER(HjPairPredicate), P, P, I64, P, P, P, P, P]),
     ("hj_comm_unique_id", I32, [P]),
     ("hj_comm_create", I32, [I32, I32, P, I32, PP]),
     ("hj_comm_free", None, [P]),

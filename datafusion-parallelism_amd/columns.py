@@ -272,6 +272,160 @@ def filter_equal_pairs(build_cols: list[DeviceColumn], probe_cols: list[DeviceCo
     return ob[:m], op[:m]
 
 
+_CMP_OPS = {"==": _lib.HJ_CMP_EQ, "=": _lib.HJ_CMP_EQ, "!=": _lib.HJ_CMP_NE, "<>": _lib.HJ_CMP_NE,
+            "<": _lib.HJ_CMP_LT, "<=": _lib.HJ_CMP_LE, ">": _lib.HJ_CMP_GT, ">=": _lib.HJ_CMP_GE}
+
+
+def _value_class(t: pa.DataType) -> int:
+    """The pair filter's value class (HJ_VAL_*) of an Arrow type; TypeError for a type the
+    device does not compare (float16, decimals, nested types, ...)."""
+    ty = pa.types
+    if ty.is_boolean(t) or ty.is_unsigned_integer(t):
+        return _lib.HJ_VAL_UINT  # a boolean is one byte, 0 / 1, on the device
+    if ty.is_signed_integer(t) or ty.is_date(t) or ty.is_timestamp(t) or ty.is_time(t) or ty.is_duration(t):
+        return _lib.HJ_VAL_INT
+    if ty.is_float32(t) or ty.is_float64(t):
+        return _lib.HJ_VAL_FLOAT
+    if _is_var(t):
+        return _lib.HJ_VAL_BYTES
+    raise TypeError(f"the device pair filter does not compare values of type {t}")
+
+
+def _plain_number(t: pa.DataType) -> bool:
+    return pa.types.is_integer(t) or pa.types.is_floating(t)
+
+
+class PairPredicate:
+    """An hj_pair_predicate over device columns: a conjunction of comparisons on the pairs
+    (build row, probe row). `terms`: (lhs, op, rhs) with lhs = ("build", i) or ("probe", i),
+    an index into `build_cols` / `probe_cols`; op one of == != < <= > >= (also = and <>);
+    rhs a column reference like lhs, or a Python scalar (a constant). The Arrow types choose
+    the value class: ints INT, uints and booleans UINT, float32 / float64 FLOAT (IEEE
+    totalOrder), date / timestamp / time / duration INT of their width (both operands of one
+    Arrow type), Utf8 / LargeUtf8 / Binary / LargeBinary BYTES (no constants). Anything else
+    - float16, decimals, signed against unsigned, int against float, a boolean against a
+    number - raises TypeError here: there is no host fallback. The object keeps the ctypes
+    arrays and the columns alive; `struct` is what the C ABI takes."""
+
+    def __init__(self, build_cols: list[DeviceColumn], probe_cols: list[DeviceColumn], terms,
+                 build_rows: int | None = None, probe_rows: int | None = None):
+        terms = list(terms)
+        if not 1 <= len(terms) <= 16:
+            raise ValueError("a pair predicate has 1..16 terms")
+        if len(build_cols) > 16 or len(probe_cols) > 16:
+            raise ValueError("a pair predicate reads at most 16 columns of each side")
+        self.build_cols, self.probe_cols = list(build_cols), list(probe_cols)
+        sides = {"build": (_lib.HJ_SIDE_BUILD, self.build_cols), "probe": (_lib.HJ_SIDE_PROBE, self.probe_cols)}
+
+        def column(ref):
+            if not (isinstance(ref, tuple) and len(ref) == 2 and ref[0] in sides):
+                return None
+            side, cols = sides[ref[0]]
+            if not 0 <= ref[1] < len(cols):
+                raise IndexError(f"{ref[0]} column {ref[1]} is outside the predicate's columns")
+            return side, int(ref[1]), cols[ref[1]]
+
+        self._terms = (_lib.HjPairTerm * len(terms))()
+        for k, (lhs, op, rhs) in enumerate(terms):
+            if op not in _CMP_OPS:
+                raise ValueError(f"term {k}: unknown comparison {op!r}")
+            lc = column(lhs)
+            if lc is None:
+                raise TypeError(f"term {k}: the left operand must be a column")
+            cls = _value_class(lc[2].type)
+            rc = column(rhs)
+            if rc is not None:
+                lt, rt = lc[2].type, rc[2].type
+                if _value_class(rt) != cls or (not (_plain_number(lt) and _plain_number(rt)) and lt != rt
+                                               and not (_is_var(lt) and _is_var(rt))):
+                    raise TypeError(f"term {k}: the device pair filter does not compare {lt} with {rt}")
+                self._terms[k] = _lib.HjPairTerm(_CMP_OPS[op], cls, lc[0], lc[1], rc[0], rc[1], 0)
+            else:
+                self._terms[k] = _lib.HjPairTerm(_CMP_OPS[op], cls, lc[0], lc[1], _lib.HJ_SIDE_CONST, 0,
+                                                 _encode_constant(rhs, lc[2].type, cls, k))
+        self._bcols = _key_columns(self.build_cols) if self.build_cols else None
+        self._pcols = _key_columns(self.probe_cols) if self.probe_cols else None
+
+        def rows(given, cols, side):
+            if given is not None:
+                return int(given)
+            if not cols:  # no column to take it from, and 0 would fail every pair
+                raise ValueError(f"{side}_rows is needed when the predicate reads no {side} column")
+            return cols[0].length
+
+        self.struct = _lib.HjPairPredicate(
+            len(terms), self._terms, len(self.build_cols), self._bcols, rows(build_rows, self.build_cols, "build"),
+            len(self.probe_cols), self._pcols, rows(probe_rows, self.probe_cols, "probe"))
+        if any(c.length < self.struct.build_rows for c in self.build_cols) or \
+                any(c.length < self.struct.probe_rows for c in self.probe_cols):
+            raise ValueError("a predicate column is shorter than its side's row count")
+
+    @property
+    def device(self):
+        return (self.build_cols or self.probe_cols)[0].device
+
+
+def _encode_constant(v, t: pa.DataType, cls: int, k: int) -> int:
+    """rhs_const of a Python scalar compared with a column of type t (as a signed int64)."""
+    if cls == _lib.HJ_VAL_BYTES:
+        raise TypeError(f"term {k}: the device pair filter takes no string / binary constants")
+    if isinstance(v, np.generic):
+        v = v.item()
+    if cls == _lib.HJ_VAL_FLOAT:
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError(f"term {k}: a {t} column needs a number, not {type(v).__name__}")
+        return int(np.float64(v).view(np.int64))
+    if pa.types.is_boolean(t):
+        if not isinstance(v, bool):
+            raise TypeError(f"term {k}: a boolean column needs a bool constant")
+        return int(v)
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise TypeError(f"term {k}: a {t} column needs an int constant, not {type(v).__name__}")
+    if cls == _lib.HJ_VAL_UINT:
+        if not 0 <= v < 2**64:
+            raise TypeError(f"term {k}: {v} is not an unsigned 64-bit value")
+        return v - 2**64 if v >= 2**63 else v
+    if not -2**63 <= v < 2**63:
+        raise TypeError(f"term {k}: {v} is not a signed 64-bit value")
+    return v
+
+
+def _pair_args(pred: PairPredicate, b: torch.Tensor, p: torch.Tensor):
+    if b.dtype != torch.int64 or p.dtype != torch.int32 or b.numel() != p.numel():
+        raise TypeError("pairs are an int64 build and an int32 probe index tensor of one length")
+    return b.contiguous(), p.contiguous(), b.numel(), b.device
+
+
+def pair_filter_test(pred: PairPredicate, b: torch.Tensor, p: torch.Tensor) -> tuple[torch.Tensor, int]:
+    """hj_pair_filter_test: the Arrow LSB bitmap (uint8 device tensor, ceil(n / 64) * 8
+    bytes) of the candidate pairs that pass the predicate, and their number."""
+    L = _lib.load()
+    b, p, n, dev = _pair_args(pred, b, p)
+    bitmap = torch.empty(max(_bitmap_bytes(n), 8), dtype=torch.uint8, device=dev)
+    if n == 0:
+        bitmap.zero_()
+    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+    check(L.hj_pair_filter_test(pred.struct, b.data_ptr() if n else None, p.data_ptr() if n else None, n,
+                                bitmap.data_ptr(), cnt.data_ptr(), _stream(dev)))
+    return bitmap, int(cnt.item())
+
+
+def pair_filter_select(pred: PairPredicate, b: torch.Tensor, p: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """hj_pair_filter_select (apply_join_filter_to_indices,
+    src/shared/datafusion_private.rs:295-328): the candidate pairs that pass the predicate,
+    order kept. Only the count comes to the host."""
+    L = _lib.load()
+    b, p, n, dev = _pair_args(pred, b, p)
+    ob = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    op = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = torch.empty(L.hj_pair_filter_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    check(L.hj_pair_filter_select(pred.struct, b.data_ptr() if n else None, p.data_ptr() if n else None, n,
+                                  ob.data_ptr(), op.data_ptr(), cnt.data_ptr(), ws.data_ptr(), _stream(dev)))
+    m = int(cnt.item())
+    return ob[:m], op[:m]
+
+
 def mark_rows(idx: torch.Tensor, nflags: int, flags: torch.Tensor | None = None) -> torch.Tensor:
     """flags[idx[i]] = 1 (uint8 device tensor of nflags; -1 / out-of-range ignored)."""
     L = _lib.load()

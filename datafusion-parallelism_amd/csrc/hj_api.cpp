@@ -2505,6 +2505,135 @@ hj_status hj_filter_equal_pairs(int ncols, const hj_key_column* build_cols, cons
     return HJ_OK;
 }
 
+// ---- pair filter (hj_pairfilter.hip) -------------------------------------------------
+
+namespace {
+// the column table of one side of a pair predicate, as key_cols() checks a key column; the
+// device-pointer test needs a GPU and is left out where none is visible
+hj_status pair_cols(const char* side, int ncols, const hj_key_column* cols, bool have_gpu, KeyCol* out) {
+    if (ncols < 0 || ncols > kMaxKeyCols)
+        return fail(HJ_ERR_INVALID, std::string("pair predicate: ") + side + " column count must be 0..16");
+    if (ncols > 0 && cols == nullptr) return fail(HJ_ERR_INVALID, std::string("pair predicate: null ") + side + " columns");
+    for (int j = 0; j < ncols; ++j) {
+        const hj_key_column& c = cols[j];
+        const std::string who = std::string("pair predicate: ") + side + " column " + std::to_string(j) + ": ";
+        const int w = c.width;
+        if (!(w == 0 || w == 1 || w == 2 || w == 4 || w == 8 || w == 16))
+            return fail(HJ_ERR_INVALID, who + "width must be 0 (variable), 1, 2, 4, 8 or 16");
+        if (w == 0 && c.offset_bytes != 4 && c.offset_bytes != 8)
+            return fail(HJ_ERR_INVALID, who + "offset_bytes must be 4 or 8");
+        if (c.values == nullptr || (w == 0 && c.offsets == nullptr)) return fail(HJ_ERR_INVALID, who + "null buffer");
+        if (c.validity_offset < 0) return fail(HJ_ERR_INVALID, who + "negative validity offset");
+        if (have_gpu && (!is_device_ptr(c.values) || !is_device_ptr(c.offsets) || !is_device_ptr(c.validity)))
+            return fail(HJ_ERR_INVALID, who + "takes device pointers");
+        out[j] = KeyCol{c.values, c.offsets, c.validity, c.validity_offset, w, c.offset_bytes};
+    }
+    return HJ_OK;
+}
+
+hj_status pair_pred(const hj_pair_predicate* p, PairPred* out) {
+    if (p == nullptr) return fail(HJ_ERR_INVALID, "null pair predicate");
+    if (p->nterms < 1 || p->nterms > kMaxPairTerms) return fail(HJ_ERR_INVALID, "pair predicate: nterms must be 1..16");
+    if (p->terms == nullptr) return fail(HJ_ERR_INVALID, "pair predicate: null terms");
+    if (p->build_rows < 0 || p->probe_rows < 0) return fail(HJ_ERR_INVALID, "pair predicate: negative row count");
+    const bool have_gpu = device_count() > 0;
+    *out = PairPred{};
+    hj_status st;
+    if ((st = pair_cols("build", p->nbuild_cols, p->build_cols, have_gpu, out->b)) != HJ_OK ||
+        (st = pair_cols("probe", p->nprobe_cols, p->probe_cols, have_gpu, out->p)) != HJ_OK)
+        return st;
+    out->nterms = p->nterms;
+    out->build_rows = p->build_rows;
+    out->probe_rows = p->probe_rows;
+    for (int k = 0; k < p->nterms; ++k) {
+        const hj_pair_term& t = p->terms[k];
+        const std::string who = "pair predicate: term " + std::to_string(k) + ": ";
+        if (t.op < HJ_CMP_EQ || t.op > HJ_CMP_GE) return fail(HJ_ERR_INVALID, who + "bad op");
+        if (t.value_class < HJ_VAL_INT || t.value_class > HJ_VAL_BYTES) return fail(HJ_ERR_INVALID, who + "bad value class");
+        if (t.lhs_side == HJ_SIDE_CONST) return fail(HJ_ERR_INVALID, who + "the left operand cannot be a constant");
+        if (t.lhs_side != HJ_SIDE_BUILD && t.lhs_side != HJ_SIDE_PROBE) return fail(HJ_ERR_INVALID, who + "bad lhs side");
+        if (t.rhs_side != HJ_SIDE_BUILD && t.rhs_side != HJ_SIDE_PROBE && t.rhs_side != HJ_SIDE_CONST)
+            return fail(HJ_ERR_INVALID, who + "bad rhs side");
+        if (t.rhs_side == HJ_SIDE_CONST && t.value_class == HJ_VAL_BYTES)
+            return fail(HJ_ERR_INVALID, who + "a BYTES term takes no constant");
+        const int sides[2] = {t.lhs_side, t.rhs_side}, cols[2] = {t.lhs_col, t.rhs_col};
+        for (int o = 0; o < 2; ++o) {
+            if (sides[o] == HJ_SIDE_CONST) continue;
+            const char* name = o == 0 ? "lhs" : "rhs";
+            const int nc = sides[o] == HJ_SIDE_BUILD ? p->nbuild_cols : p->nprobe_cols;
+            if (cols[o] < 0 || cols[o] >= nc)
+                return fail(HJ_ERR_INVALID, who + name + " column index outside its side's columns");
+            const int w = (sides[o] == HJ_SIDE_BUILD ? out->b : out->p)[cols[o]].width;
+            const bool ok = t.value_class == HJ_VAL_BYTES   ? w == 0
+                            : t.value_class == HJ_VAL_FLOAT ? (w == 4 || w == 8)
+                                                            : (w == 1 || w == 2 || w == 4 || w == 8);
+            if (!ok)
+                return fail(HJ_ERR_INVALID, who + name + " column width " + std::to_string(w) +
+                                                " is not one its value class takes");
+        }
+        out->t[k] = PairTerm{t.op, t.value_class, t.lhs_side, t.lhs_col, t.rhs_side,
+                             t.rhs_side == HJ_SIDE_CONST ? 0 : t.rhs_col, t.rhs_const};
+    }
+    return HJ_OK;
+}
+
+bool ranges_overlap(const void* a, const void* b, int64_t bytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + (uintptr_t)bytes && y < x + (uintptr_t)bytes;
+}
+constexpr int64_t kMaxPairFilterRows = (int64_t)1 << 40;
+}  // namespace
+
+hj_status hj_pair_predicate_check(const hj_pair_predicate* p) {
+    PairPred pr;
+    return pair_pred(p, &pr);
+}
+
+hj_status hj_pair_filter_test(const hj_pair_predicate* p, const uint64_t* build_idx, const uint32_t* probe_idx,
+                              int64_t n, uint8_t* out_bitmap, int64_t* d_count, void* stream) {
+    PairPred pr;
+    hj_status st = pair_pred(p, &pr);
+    if (st != HJ_OK) return st;
+    if (device_count() == 0) return fail(HJ_ERR_NO_DEVICE, "no GPU visible");
+    if (n < 0 || n >= kMaxPairFilterRows) return fail(HJ_ERR_INVALID, "hj_pair_filter_test: n must lie in [0, 2^40)");
+    if (d_count == nullptr || (n > 0 && (build_idx == nullptr || probe_idx == nullptr || out_bitmap == nullptr)))
+        return fail(HJ_ERR_INVALID, "hj_pair_filter_test: null pointer");
+    if ((reinterpret_cast<uintptr_t>(out_bitmap) & 7) || (reinterpret_cast<uintptr_t>(d_count) & 7) ||
+        (reinterpret_cast<uintptr_t>(build_idx) & 7) || (reinterpret_cast<uintptr_t>(probe_idx) & 3))
+        return fail(HJ_ERR_INVALID, "hj_pair_filter_test: misaligned pointer");
+    if (!is_device_ptr(build_idx) || !is_device_ptr(probe_idx) || !is_device_ptr(out_bitmap) || !is_device_ptr(d_count))
+        return fail(HJ_ERR_INVALID, "hj_pair_filter_test takes device pointers");
+    HIP_TRY(launch_pair_filter_test(pr, build_idx, probe_idx, n, out_bitmap, d_count, (hipStream_t)stream));
+    return HJ_OK;
+}
+
+int64_t hj_pair_filter_workspace_bytes(int64_t n) { return pair_filter_workspace(n < 0 ? 0 : n); }
+
+hj_status hj_pair_filter_select(const hj_pair_predicate* p, const uint64_t* build_idx, const uint32_t* probe_idx,
+                                int64_t n, uint64_t* out_build, uint32_t* out_probe, int64_t* d_count, void* workspace,
+                                void* stream) {
+    PairPred pr;
+    hj_status st = pair_pred(p, &pr);
+    if (st != HJ_OK) return st;
+    if (device_count() == 0) return fail(HJ_ERR_NO_DEVICE, "no GPU visible");
+    if (n < 0 || n >= kMaxPairFilterRows) return fail(HJ_ERR_INVALID, "hj_pair_filter_select: n must lie in [0, 2^40)");
+    if (d_count == nullptr || workspace == nullptr ||
+        (n > 0 && (build_idx == nullptr || probe_idx == nullptr || out_build == nullptr || out_probe == nullptr)))
+        return fail(HJ_ERR_INVALID, "hj_pair_filter_select: null pointer");
+    if ((reinterpret_cast<uintptr_t>(out_build) & 7) || (reinterpret_cast<uintptr_t>(out_probe) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_count) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
+        (reinterpret_cast<uintptr_t>(build_idx) & 7) || (reinterpret_cast<uintptr_t>(probe_idx) & 3))
+        return fail(HJ_ERR_INVALID, "hj_pair_filter_select: misaligned pointer");
+    if (n > 0 && (ranges_overlap(out_build, build_idx, 8 * n) || ranges_overlap(out_probe, probe_idx, 4 * n)))
+        return fail(HJ_ERR_INVALID, "hj_pair_filter_select: outputs must not overlap the candidate pairs");
+    if (!is_device_ptr(build_idx) || !is_device_ptr(probe_idx) || !is_device_ptr(out_build) ||
+        !is_device_ptr(out_probe) || !is_device_ptr(d_count) || !is_device_ptr(workspace))
+        return fail(HJ_ERR_INVALID, "hj_pair_filter_select takes device pointers");
+    HIP_TRY(launch_pair_filter_select(pr, build_idx, probe_idx, n, out_build, out_probe, d_count, workspace,
+                                      (hipStream_t)stream));
+    return HJ_OK;
+}
+
 hj_status hj_gen_perm_keys(int64_t* out, int64_t n, int64_t mul, int64_t range, void* stream) {
     if (device_count() == 0) return fail(HJ_ERR_NO_DEVICE, "no GPU visible");
     if (range <= 0 || n < 0) return fail(HJ_ERR_INVALID, "bad range");

@@ -263,6 +263,34 @@ hipError_t launch_equal_pairs(const KeyCols& bc, const KeyCols& pc, const uint64
                               int64_t n, uint64_t* out_b, uint32_t* out_p, int64_t* d_count, void* ws,
                               hipStream_t s);
 
+// ---- pair filter (hj_pairfilter.hip) -------------------------------------------
+// A conjunction of comparisons on candidate pairs, as the kernels see it (include/hj.h,
+// hj_pair_predicate, checked by the caller): op 0..5 = EQ NE LT LE GT GE; cls, side as below.
+constexpr int kPfInt = 0, kPfUint = 1, kPfFloat = 2, kPfBytes = 3;
+constexpr int kPfBuild = 0, kPfProbe = 1, kPfConst = 2;
+constexpr int kMaxPairTerms = 16;
+struct PairTerm {
+    int op, cls;
+    int lhs_side, lhs_col;
+    int rhs_side, rhs_col;
+    int64_t rhs_const;
+};
+struct PairPred {
+    PairTerm t[kMaxPairTerms];
+    KeyCol b[kMaxKeyCols], p[kMaxKeyCols];
+    int64_t build_rows, probe_rows;
+    int nterms;
+};
+// out_bitmap: ceil(n / 64) u64 words, bit i = pair i passes; *d_count = set bits
+hipError_t launch_pair_filter_test(const PairPred& pr, const uint64_t* bidx, const uint32_t* pidx, int64_t n,
+                                   uint8_t* out_bitmap, int64_t* d_count, hipStream_t s);
+// the passing pairs in order (capacity n), *d_count their number; workspace (8-byte
+// aligned): pair_filter_workspace(n)
+int64_t pair_filter_workspace(int64_t n);
+hipError_t launch_pair_filter_select(const PairPred& pr, const uint64_t* bidx, const uint32_t* pidx, int64_t n,
+                                     uint64_t* out_b, uint32_t* out_p, int64_t* d_count, void* workspace,
+                                     hipStream_t s);
+
 // ---- generators ----------------------------------------------------------
 hipError_t launch_gen_perm(int64_t* out, int64_t n, int64_t mul, int64_t range, hipStream_t s);
 hipError_t launch_gen_uniform(int64_t* out, int64_t n, uint64_t seed, int64_t range,

@@ -1,0 +1,279 @@
+// hj_pairfilter.hip — gfx950 kernels of the pair filter (include/hj.h, "pair filter"): a
+// conjunction of typed comparisons between build columns, probe columns and constants,
+// evaluated on candidate pairs. Replaces apply_join_filter_to_indices
+// (src/shared/datafusion_private.rs:295-328) for predicates of that form.
+//
+//   pair_eval_kernel      one pair per lane, whole waves of 64 pairs: the wave's 64 results
+//                         are one ballot word (lane 0 stores it, no atomics on the bitmap);
+//                         the popcounts go to the tile's total (select) or to the count (test).
+//                         The predicate travels as a kernel argument, so every descriptor -
+//                         class, width, op, column - is wave-uniform and the switches over
+//                         them are scalar branches; only the operand gathers and the BYTES
+//                         compare loop are per lane. BYTES = false leaves that loop out.
+//   pair_compact_kernel   per tile of 4096 pairs: re-reads the tile's 64 ballot words and
+//                         writes each passing pair at tile offset (scanned tile totals) +
+//                         word offset (wave scan of the popcounts) + bit rank. No workgroup
+//                         waits on another.
+//
+// HBM-bound: 12 bytes of pair read per candidate, the operand gathers, one bit written.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "hj_device.h"
+#include "hj_launch.h"
+#include "hj_util.h"
+
+namespace dfp {
+
+constexpr int kPfThreads = 256;
+constexpr int kPfWaves = kPfThreads / 64;
+constexpr int kPfWords = 64;                // ballot words (of 64 pairs) per tile
+constexpr int kPfTile = kPfWords * 64;      // 4096 pairs
+constexpr int kPfSteps = kPfWords / kPfWaves;
+constexpr unsigned kPfMaxGrid = 4096;       // grid-stride over the tiles beyond this
+
+// One fixed-width operand as 64 bits, sign- (INT) or zero-extended; the column is
+// wave-uniform, so the width switch and the alignment test are scalar branches.
+__device__ __forceinline__ uint64_t pf_fixed_bits(const KeyCol& c, int64_t row, bool sign) {
+    const uint8_t* p = reinterpret_cast<const uint8_t*>(c.values) + row * c.width;
+    const bool aligned = (reinterpret_cast<uintptr_t>(c.values) & (uintptr_t)(c.width - 1)) == 0;
+    uint64_t v;
+    if (aligned) {
+        switch (c.width) {
+            case 1: v = *p; break;
+            case 2: v = *reinterpret_cast<const uint16_t*>(p); break;
+            case 4: v = *reinterpret_cast<const uint32_t*>(p); break;
+            default: v = *reinterpret_cast<const uint64_t*>(p); break;
+        }
+    } else {
+        v = 0;
+        for (int i = 0; i < c.width; ++i) v |= (uint64_t)p[i] << (8 * i);
+    }
+    if (sign && c.width < 8) {
+        const int sh = 64 - 8 * c.width;
+        v = (uint64_t)((int64_t)(v << sh) >> sh);
+    }
+    return v;
+}
+
+// The comparison key of one fixed-width operand: signed order of the keys = the class's
+// order of the values. INT: the value; UINT: the value with the top bit flipped; FLOAT: the
+// double's totalOrder key b ^ ((b >> 63) & INT64_MAX), a float32 widened first.
+__device__ __forceinline__ int64_t pf_float_key(uint64_t bits) {
+    const int64_t b = (int64_t)bits;
+    return b ^ ((b >> 63) & INT64_MAX);
+}
+
+__device__ __forceinline__ int64_t pf_fixed_key(const KeyCol& c, int64_t row, int cls) {
+    if (cls == kPfFloat) {
+        uint64_t bits = pf_fixed_bits(c, row, false);
+        if (c.width == 4) bits = (uint64_t)__double_as_longlong((double)__uint_as_float((uint32_t)bits));
+        return pf_float_key(bits);
+    }
+    const uint64_t v = pf_fixed_bits(c, row, cls == kPfInt);
+    return (int64_t)(cls == kPfUint ? v ^ (1ull << 63) : v);
+}
+
+__device__ __forceinline__ int64_t pf_const_key(int64_t k, int cls) {
+    if (cls == kPfFloat) return pf_float_key((uint64_t)k);
+    return cls == kPfUint ? (int64_t)((uint64_t)k ^ (1ull << 63)) : k;
+}
+
+__device__ __forceinline__ void pf_var_range(const KeyCol& c, int64_t row, int64_t* a, int64_t* b) {
+    if (c.offset_bytes == 8) {
+        const int64_t* o = reinterpret_cast<const int64_t*>(c.offsets);
+        *a = o[row];
+        *b = o[row + 1];
+    } else {
+        const int32_t* o = reinterpret_cast<const int32_t*>(c.offsets);
+        *a = o[row];
+        *b = o[row + 1];
+    }
+}
+
+// -1 / 0 / 1: lexicographic order on unsigned bytes, a proper prefix is smaller
+__device__ __forceinline__ int pf_bytes_cmp(const KeyCol& x, int64_t xr, const KeyCol& y, int64_t yr) {
+    int64_t xa, xb, ya, yb;
+    pf_var_range(x, xr, &xa, &xb);
+    pf_var_range(y, yr, &ya, &yb);
+    const uint8_t* xp = reinterpret_cast<const uint8_t*>(x.values) + xa;
+    const uint8_t* yp = reinterpret_cast<const uint8_t*>(y.values) + ya;
+    const int64_t lx = xb - xa, ly = yb - ya, m = lx < ly ? lx : ly;
+    for (int64_t i = 0; i < m; ++i) {
+        const int d = (int)xp[i] - (int)yp[i];
+        if (d != 0) return d < 0 ? -1 : 1;
+    }
+    return lx < ly ? -1 : (lx > ly ? 1 : 0);
+}
+
+__device__ __forceinline__ bool pf_compare(int op, int64_t x, int64_t y) {
+    switch (op) {
+        case 0: return x == y;
+        case 1: return x != y;
+        case 2: return x < y;
+        case 3: return x <= y;
+        case 4: return x > y;
+        default: return x >= y;
+    }
+}
+
+// whether pair (b, p) passes every term; `live` is false for lanes past n
+template <bool BYTES>
+__device__ __forceinline__ bool pf_pair_passes(const PairPred& pr, bool live, uint64_t b, uint32_t p) {
+    bool pass = live && b < (uint64_t)pr.build_rows && (int64_t)p < pr.probe_rows;
+    for (int t = 0; t < pr.nterms; ++t) {  // uniform trip count and descriptors
+        const PairTerm& tm = pr.t[t];
+        const KeyCol& lc = tm.lhs_side == kPfBuild ? pr.b[tm.lhs_col] : pr.p[tm.lhs_col];
+        const int64_t lrow = tm.lhs_side == kPfBuild ? (int64_t)b : (int64_t)p;
+        const bool rconst = tm.rhs_side == kPfConst;
+        const KeyCol& rc = tm.rhs_side == kPfBuild ? pr.b[rconst ? 0 : tm.rhs_col] : pr.p[rconst ? 0 : tm.rhs_col];
+        const int64_t rrow = tm.rhs_side == kPfBuild ? (int64_t)b : (int64_t)p;
+        if (pass) {  // per lane: a failed or out-of-range pair dereferences nothing
+            bool ok = bit_valid(lc.valid, lc.voff, lrow) && (rconst || bit_valid(rc.valid, rc.voff, rrow));
+            if (ok) {
+                int64_t x, y;
+                if (BYTES && tm.cls == kPfBytes) {
+                    x = pf_bytes_cmp(lc, lrow, rc, rrow);
+                    y = 0;
+                } else {
+                    x = pf_fixed_key(lc, lrow, tm.cls);
+                    y = rconst ? pf_const_key(tm.rhs_const, tm.cls) : pf_fixed_key(rc, rrow, tm.cls);
+                }
+                ok = pf_compare(tm.op, x, y);
+            }
+            pass = ok;
+        }
+    }
+    return pass;
+}
+
+// words: the ballot words, word w covers pairs [64 w, 64 w + 64); only words < nwords are
+// stored (test: ceil(n / 64); select: every word of every tile). ttot (select): the tile's
+// passing pairs; d_count (test): += the block's passing pairs, zeroed by the launcher.
+template <bool BYTES>
+__global__ void __launch_bounds__(kPfThreads)
+pair_eval_kernel(PairPred pr, const uint64_t* __restrict__ bidx, const uint32_t* __restrict__ pidx, int64_t n,
+                 int64_t ntiles, unsigned long long* __restrict__ words, int64_t nwords,
+                 unsigned long long* __restrict__ ttot, unsigned long long* __restrict__ d_count) {
+    __shared__ unsigned int s_c[kPfWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long block_cnt = 0;  // thread 0's
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t tile0 = tile * kPfTile;
+        unsigned int cnt = 0;
+#pragma unroll 1
+        for (int s0 = 0; s0 < kPfSteps; ++s0) {
+            const int64_t i = tile0 + (int64_t)s0 * kPfThreads + threadIdx.x;
+            const bool live = i < n;
+            uint64_t b = 0;
+            uint32_t p = 0;
+            if (live) {
+                b = bidx[i];
+                p = pidx[i];
+            }
+            const bool pass = pf_pair_passes<BYTES>(pr, live, b, p);
+            const unsigned long long word = __ballot(pass);  // whole wave: EXEC is full here
+            const int64_t w = (i - lane) >> 6;
+            if (lane == 0) {
+                if (w < nwords) words[w] = word;
+                cnt += (unsigned int)__popcll(word);
+            }
+        }
+        if (lane == 0) s_c[wave] = cnt;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long t = 0;
+#pragma unroll
+            for (int k = 0; k < kPfWaves; ++k) t += s_c[k];
+            if (ttot != nullptr) ttot[tile] = t;
+            block_cnt += t;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && d_count != nullptr && block_cnt != 0) atomicAdd(d_count, block_cnt);
+}
+
+// toff: the scanned tile totals; out_b / out_p hold n elements and every position is below
+// the total <= n; a set bit names a pair < n (the evaluate kernel sets none past n)
+__global__ void __launch_bounds__(kPfThreads)
+pair_compact_kernel(const uint64_t* __restrict__ bidx, const uint32_t* __restrict__ pidx, int64_t ntiles,
+                    const unsigned long long* __restrict__ words, const unsigned long long* __restrict__ toff,
+                    uint64_t* __restrict__ out_b, uint32_t* __restrict__ out_p) {
+    __shared__ unsigned long long s_b[kPfWords];
+    __shared__ unsigned int s_off[kPfWords];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        if (wave == 0) {
+            const unsigned long long w = words[tile * kPfWords + lane];
+            const unsigned int c = (unsigned int)__popcll(w);
+            s_b[lane] = w;
+            s_off[lane] = wave_incl_scan(c) - c;
+        }
+        __syncthreads();
+        const unsigned long long t0 = toff[tile];
+        const int64_t tile0 = tile * kPfTile;
+        for (int j = wave; j < kPfWords; j += kPfWaves) {
+            const unsigned long long w = s_b[j];
+            if ((w >> lane) & 1) {
+                const int64_t i = tile0 + (int64_t)j * 64 + lane;
+                const unsigned long long pos = t0 + s_off[j] + (unsigned int)__popcll(w & ((1ull << lane) - 1));
+                out_b[pos] = bidx[i];
+                out_p[pos] = pidx[i];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+static int64_t pf_tiles(int64_t n) { return (n + kPfTile - 1) / kPfTile; }
+
+static bool pf_has_bytes(const PairPred& pr) {
+    for (int t = 0; t < pr.nterms; ++t)
+        if (pr.t[t].cls == kPfBytes) return true;
+    return false;
+}
+
+static hipError_t pf_eval(const PairPred& pr, const uint64_t* bidx, const uint32_t* pidx, int64_t n, int64_t nt,
+                          unsigned long long* words, int64_t nwords, unsigned long long* ttot,
+                          unsigned long long* d_count, hipStream_t s) {
+    const unsigned grid = (unsigned)std::min<int64_t>(nt, kPfMaxGrid);
+    if (pf_has_bytes(pr))
+        pair_eval_kernel<true><<<grid, kPfThreads, 0, s>>>(pr, bidx, pidx, n, nt, words, nwords, ttot, d_count);
+    else
+        pair_eval_kernel<false><<<grid, kPfThreads, 0, s>>>(pr, bidx, pidx, n, nt, words, nwords, ttot, d_count);
+    return hipGetLastError();
+}
+
+hipError_t launch_pair_filter_test(const PairPred& pr, const uint64_t* bidx, const uint32_t* pidx, int64_t n,
+                                   uint8_t* out_bitmap, int64_t* d_count, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(d_count, 0, 8, s);
+    if (e != hipSuccess || n <= 0) return e;
+    return pf_eval(pr, bidx, pidx, n, pf_tiles(n), (unsigned long long*)out_bitmap, (n + 63) / 64, nullptr,
+                   (unsigned long long*)d_count, s);
+}
+
+// tile totals u64[nt + 2], ballot words u64[64 nt], the scan's scratch: about one bit per pair
+int64_t pair_filter_workspace(int64_t n) {
+    const int64_t nt = pf_tiles(n);
+    return 8 * (nt + 2) + 8 * nt * kPfWords + scan_scratch_bytes(nt) + 64;
+}
+
+hipError_t launch_pair_filter_select(const PairPred& pr, const uint64_t* bidx, const uint32_t* pidx, int64_t n,
+                                     uint64_t* out_b, uint32_t* out_p, int64_t* d_count, void* workspace,
+                                     hipStream_t s) {
+    const int64_t nt = pf_tiles(n);
+    if (nt == 0) return hipMemsetAsync(d_count, 0, 8, s);
+    unsigned long long* ttot = (unsigned long long*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+    unsigned long long* words = ttot + (nt + 2);
+    void* scratch = words + nt * kPfWords;
+    hipError_t e = pf_eval(pr, bidx, pidx, n, nt, words, nt * kPfWords, ttot, nullptr, s);
+    if (e != hipSuccess) return e;
+    if ((e = launch_scan_u64(ttot, nt, scratch, (unsigned long long*)d_count, s)) != hipSuccess) return e;
+    const unsigned grid = (unsigned)std::min<int64_t>(nt, (int64_t)kPfMaxGrid * 16);
+    pair_compact_kernel<<<grid, kPfThreads, 0, s>>>(bidx, pidx, nt, words, ttot, out_b, out_p);
+    return hipGetLastError();
+}
+
+}  // namespace dfp

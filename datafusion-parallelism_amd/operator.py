@@ -27,7 +27,8 @@ whose build and probe run on the gfx950 kernels through the C ABI (``include/hj.
     RightSemi, RightAnti                                      JoinType + _probe_batch /
                                                               _finalize_build_side
   apply_join_filter_to_indices (src/shared/datafusion_private.rs:295-328)
-                                                              JoinFilter
+                                                              JoinFilter (host callable),
+                                                              CompareFilter (device, hj_pair_filter_select)
 
 Join keys: one Int32/Int64 column goes to the table as is (exact keys); several key
 columns, or a key of any other fixed-width or Utf8/Binary type, go through
@@ -51,8 +52,8 @@ import pyarrow.compute as pc
 import torch
 
 from ._lib import HjError, HJ_ERR_INVALID
-from .columns import (DeviceColumn, DeviceRecordBatch, composite_keys, filter_equal_pairs, mark_rows, select_bitmap,
-                      select_rows)
+from .columns import (DeviceColumn, DeviceRecordBatch, PairPredicate, composite_keys, filter_equal_pairs, mark_rows,
+                      pair_filter_select, select_bitmap, select_rows)
 from .key_filter import KeyFilter
 from .table import HashTable
 
@@ -132,6 +133,113 @@ class JoinFilter:
         self.expression = expression
         self.left_columns = left_columns
         self.right_columns = right_columns
+
+
+class L:
+    """A build (left) column of a CompareFilter term, by name."""
+
+    def __init__(self, name: str):
+        self.name = name
+
+    def __repr__(self):
+        return f"L({self.name!r})"
+
+
+class R:
+    """A probe (right) column of a CompareFilter term, by name."""
+
+    def __init__(self, name: str):
+        self.name = name
+
+    def __repr__(self):
+        return f"R({self.name!r})"
+
+
+_FLIP = {"==": "==", "=": "==", "!=": "!=", "<>": "!=", "<": ">", "<=": ">=", ">": "<", ">=": "<="}
+_PC_OPS = {"==": pc.equal, "=": pc.equal, "!=": pc.not_equal, "<>": pc.not_equal, "<": pc.less,
+           "<=": pc.less_equal, ">": pc.greater, ">=": pc.greater_equal}
+
+
+class CompareFilter:
+    """A declarative non-equi join condition that runs on the device: a conjunction of
+    comparisons between build columns (`L(name)`), probe columns (`R(name)`) and constants
+    (bare Python scalars), e.g.
+
+        CompareFilter([(L("value"), "!=", R("value")), (R("ts"), ">=", L("lo")), (L("qty"), "<", 10)])
+
+    The candidate pairs are filtered by hj_pair_filter_select over the resident build and
+    probe columns (apply_join_filter_to_indices, src/shared/datafusion_private.rs:295-328):
+    no column is gathered and only the count of survivors comes to the host. Operators:
+    == != < <= > >= (also = and <>). A null operand fails the pair. Floats compare in IEEE
+    totalOrder (include/hj.h): unlike pyarrow, NaN equals the NaN of the same bits and
+    -0.0 < +0.0. Types the device does not compare (columns.PairPredicate) raise TypeError at
+    the first probe batch; there is no host fallback. `as_callable()` gives the equivalent
+    JoinFilter for the host path."""
+
+    def __init__(self, terms):
+        self.terms = []
+        for lhs, op, rhs in terms:
+            if op not in _FLIP:
+                raise ValueError(f"unknown comparison {op!r}")
+            if not isinstance(lhs, (L, R)):
+                if not isinstance(rhs, (L, R)):
+                    raise ValueError("a term compares at least one column")
+                lhs, op, rhs = rhs, _FLIP[op], lhs  # constant on the left: c < x is x > c
+            self.terms.append((lhs, op, rhs))
+        if not 1 <= len(self.terms) <= 16:
+            raise ValueError("a CompareFilter has 1..16 terms")
+
+    def _names(self, kind) -> list[str]:
+        out = []
+        for lhs, _, rhs in self.terms:
+            for x in (lhs, rhs):
+                if isinstance(x, kind) and x.name not in out:
+                    out.append(x.name)
+        return out
+
+    def predicate(self, build_cols: Sequence[DeviceColumn], build_names: Sequence[str],
+                  probe_cols: Sequence[DeviceColumn], probe_names: Sequence[str], build_rows: int,
+                  probe_rows: int) -> PairPredicate:
+        """The PairPredicate over the columns the terms name (each column listed once)."""
+        lnames, rnames = self._names(L), self._names(R)
+        bnames, pnames = list(build_names), list(probe_names)
+
+        def ref(x):
+            if isinstance(x, L):
+                return ("build", lnames.index(x.name))
+            if isinstance(x, R):
+                return ("probe", rnames.index(x.name))
+            return x
+
+        for n, names, side in [(n, bnames, "build") for n in lnames] + [(n, pnames, "probe") for n in rnames]:
+            if n not in names:
+                raise HjError(HJ_ERR_INVALID, f"CompareFilter: the {side} side has no column {n!r}")
+        return PairPredicate([build_cols[bnames.index(n)] for n in lnames],
+                             [probe_cols[pnames.index(n)] for n in rnames],
+                             [(ref(a), op, ref(b)) for a, op, b in self.terms], build_rows, probe_rows)
+
+    def as_callable(self) -> "JoinFilter":
+        """The same condition as a host JoinFilter over pyarrow compute calls (IEEE float
+        comparison there: it differs from the device path on NaN and signed zeros only)."""
+        terms = list(self.terms)
+
+        def expression(left: pa.RecordBatch, right: pa.RecordBatch) -> pa.Array:
+            def operand(x, other):
+                if isinstance(x, L):
+                    return left.column(x.name)
+                if isinstance(x, R):
+                    return right.column(x.name)
+                t = other.type
+                return pa.scalar(x) if pa.types.is_floating(t) else pa.scalar(x, type=t)
+
+            mask = None
+            for lhs, op, rhs in terms:
+                a = operand(lhs, None)
+                m = _PC_OPS[op](a, operand(rhs, a))
+                mask = m if mask is None else pc.and_kleene(mask, m)
+            return mask
+
+        return JoinFilter(expression, self._names(L), self._names(R))
 
 
 def _batch(cols: Sequence[DeviceColumn], names: Sequence[str]) -> pa.RecordBatch:
@@ -430,12 +538,16 @@ class BuildImplementation:
         return consumer.call(GpuIndexLookup(table, sh), sh.concatenated())
 
 
-def _apply_filter(flt: JoinFilter, build_cols: list[DeviceColumn], build_names: Sequence[str],
+def _apply_filter(flt: "JoinFilter | CompareFilter", build_cols: list[DeviceColumn], build_names: Sequence[str],
                   probe_cols: list[DeviceColumn], probe_names: Sequence[str], b: torch.Tensor, p: torch.Tensor):
     """apply_join_filter_to_indices: evaluate the filter on the candidate rows, keep the
     pairs where it is true (order preserved)."""
     if b.numel() == 0:
         return b, p
+    if isinstance(flt, CompareFilter):  # on the device: nothing is gathered or copied to the host
+        nb = build_cols[0].length if build_cols else 0
+        np_ = probe_cols[0].length if probe_cols else 0
+        return pair_filter_select(flt.predicate(build_cols, build_names, probe_cols, probe_names, nb, np_), b, p)
     lsel = [i for i, n in enumerate(build_names) if flt.left_columns is None or n in flt.left_columns]
     rsel = [i for i, n in enumerate(probe_names) if flt.right_columns is None or n in flt.right_columns]
     left = _batch([build_cols[i].take(b) for i in lsel], [build_names[i] for i in lsel])
@@ -463,7 +575,7 @@ def _takes_match_path(jt: JoinType, filter, lookup: GpuIndexLookup, key_cols: Se
 
 
 def probe_batch(join_type: JoinType, probe_expressions: Sequence[str | int], build_expressions: Sequence[str | int],
-                filter: JoinFilter | None, build_side_records: pa.RecordBatch, read_only_join_map: GpuIndexLookup,
+                filter: "JoinFilter | CompareFilter | None", build_side_records: pa.RecordBatch, read_only_join_map: GpuIndexLookup,
                 probe_batch: pa.RecordBatch, build_visited: torch.Tensor | None = None
                 ) -> pa.RecordBatch | list[pa.RecordBatch] | None:
     """One probe batch of any join type: the lookup_*_probe_batch functions of
@@ -521,7 +633,7 @@ def _row_chunks(rows: torch.Tensor, limit: int) -> list[torch.Tensor]:
     return [rows[lo:lo + limit] for lo in range(0, rows.numel(), limit)] or [rows]
 
 
-def _probe_batch_windowed(jt: JoinType, filter: JoinFilter | None, build_side_records: pa.RecordBatch,
+def _probe_batch_windowed(jt: JoinType, filter: "JoinFilter | CompareFilter | None", build_side_records: pa.RecordBatch,
                           lookup: GpuIndexLookup, probe_batch: pa.RecordBatch, probe_cols: list[DeviceColumn],
                           key_cols: list[DeviceColumn], build_visited: torch.Tensor | None,
                           limit: int) -> list[pa.RecordBatch]:
@@ -681,13 +793,14 @@ class _ProbeConsumer:
 class ParallelHashJoin:
     """src/operator/parallel_hash_join.rs:16-168: `left` is the build side, `right` the
     probe side, each a list of partitions (lists of RecordBatches); `join_type` one of
-    JoinType (names as DataFusion's); `filter` an optional JoinFilter. Output
+    JoinType (names as DataFusion's); `filter` an optional JoinFilter (host
+    callable) or CompareFilter (comparisons, filtered on the device). Output
     partitioning follows the probe side (RoundRobinBatch(N), 85-91); build-side rows of
     Left / Full / LeftSemi / LeftAnti joins come from the last partition to finish."""
 
     def __init__(self, left: list[list[pa.RecordBatch]], right: list[list[pa.RecordBatch]],
                  on: Sequence[tuple[str, str]], join_type: JoinType | str = JoinType.Inner, device: int = 0,
-                 replacement: JoinReplacement = JoinReplacement.Gpu, filter: JoinFilter | None = None,
+                 replacement: JoinReplacement = JoinReplacement.Gpu, filter: "JoinFilter | CompareFilter | None" = None,
                  right_schema: pa.Schema | None = None, devices: Sequence[int] | None = None, plan: str = "auto",
                  prefilter: bool = False, match_probe: bool = False, max_output_rows: int | None = None):
         """max_output_rows: None, or the most rows any output batch, pair buffer or gathered

@@ -700,6 +700,102 @@ hj_status hj_filter_equal_pairs(int ncols, const hj_key_column* build_cols,
                                 uint32_t* out_probe, int64_t* d_count, void* workspace,
                                 void* stream);
 
+/* ---- pair filter: a conjunction of typed comparisons between build columns, probe
+ *      columns and constants, evaluated on candidate pairs in device memory. Replaces
+ *      apply_join_filter_to_indices (src/shared/datafusion_private.rs:295-328) for join
+ *      filters of that form (ON l.k = r.k AND l.a != r.a AND r.ts >= l.lo AND l.qty < 10):
+ *      the reference evaluates a physical expression over the gathered candidate rows; here
+ *      no row is gathered and nothing leaves the device. Opt-in: nothing else in the library
+ *      calls it. Device pointers only, asynchronous on `stream`, no allocation and no host
+ *      synchronisation.
+ *
+ * Pair pass rule. Pair i passes iff build_idx[i] < build_rows and probe_idx[i] <
+ * probe_rows and every term is true. An out-of-range index - the outer joins' all-ones
+ * null index included - is never dereferenced: the pair simply fails (hj_mark_rows skips
+ * such indices in the same way). A term reads row build_idx[i] of a build column, row
+ * probe_idx[i] of a probe column. A term with a null operand (validity bit 0) is not true:
+ * SQL's three-valued AND over a conjunction reduces to this, and so does the reference's
+ * "null counts as false".
+ *
+ * Value classes. Both operands of a term are of the term's class.
+ *   HJ_VAL_INT / HJ_VAL_UINT: fixed width 1, 2, 4 or 8. Each operand is sign- (INT) or
+ *     zero- (UINT) extended to 64 bits, so the two operands may differ in width; compared as
+ *     int64 / uint64. rhs_const is the int64 value / the uint64's bits.
+ *   HJ_VAL_FLOAT: width 4 (IEEE binary32, widened to double) or 8 (double); rhs_const is the
+ *     bits of a double. Compared in IEEE totalOrder, as the reference's engine does
+ *     (DataFusion 40 compares with arrow-rs cmp::*, and hj_filter_equal_pairs compares floats
+ *     by their bits): with b the double's bits as int64, the key is
+ *     b ^ ((b >> 63) & INT64_MAX) (arithmetic shift), and keys compare as signed int64. So
+ *     -0.0 < +0.0, a NaN equals the NaN of the same bits, and a positive NaN is above +inf.
+ *   HJ_VAL_BYTES: variable width (width 0, offsets of 4 or 8 bytes; the two sides may
+ *     differ in offset width). Compared lexicographically on unsigned bytes, a proper prefix
+ *     is smaller: arrow's order for Utf8 and Binary. No constant operand.
+ *
+ * Columns are hj_key_column; build columns index the build side's concatenated rows
+ * (build_rows of them), probe columns the probe batch's rows (probe_rows). A fixed-width
+ * column of another width (16) may be listed but no term can name it.
+ *
+ * Sizes. n in [0, 2^40); n == 0 is valid and still writes *d_count. */
+enum { HJ_CMP_EQ = 0, HJ_CMP_NE, HJ_CMP_LT, HJ_CMP_LE, HJ_CMP_GT, HJ_CMP_GE };
+enum { HJ_VAL_INT = 0, HJ_VAL_UINT = 1, HJ_VAL_FLOAT = 2, HJ_VAL_BYTES = 3 };
+enum { HJ_SIDE_BUILD = 0, HJ_SIDE_PROBE = 1, HJ_SIDE_CONST = 2 };
+
+typedef struct hj_pair_term {
+    int op;                  /* HJ_CMP_*: lhs op rhs */
+    int value_class;         /* HJ_VAL_*: both operands are of this class */
+    int lhs_side, lhs_col;   /* BUILD or PROBE, index into that side's columns */
+    int rhs_side, rhs_col;   /* BUILD, PROBE, or CONST (rhs_col ignored) */
+    int64_t rhs_const;       /* CONST: int64 / uint64 bits / the bits of a double */
+} hj_pair_term;
+
+typedef struct hj_pair_predicate {
+    int nterms;                       /* 1..16 */
+    const hj_pair_term* terms;        /* host memory */
+    int nbuild_cols;                  /* 0..16 */
+    const hj_key_column* build_cols;  /* host memory (the buffers inside: device) */
+    int64_t build_rows;
+    int nprobe_cols;                  /* 0..16 */
+    const hj_key_column* probe_cols;
+    int64_t probe_rows;
+} hj_pair_predicate;
+
+/* Validates a predicate; needs no GPU. HJ_ERR_INVALID, with a message that names the term
+ * (hj_last_error), for: a null predicate or term array, nterms outside 1..16, a column count
+ * outside 0..16, a negative row count; a column as hj_composite_keys rejects it (a bad
+ * width or offset width, a null buffer, a negative validity offset, and - where a GPU is
+ * visible to tell - a host pointer); a bad op, class or side; lhs_side == HJ_SIDE_CONST; a
+ * column index outside its side; a column width the class does not take; a BYTES constant.
+ * New (the reference's filter is a compiled physical expression; replaces the planning half
+ * of apply_join_filter_to_indices, src/shared/datafusion_private.rs:295-328). */
+hj_status hj_pair_predicate_check(const hj_pair_predicate* p);
+
+/* out_bitmap: Arrow LSB bitmap, 8-byte aligned, ceil(n / 64) * 8 bytes. Bit i is set iff
+ * pair i passes. Every word is written in full and bits at and beyond n are 0: the caller
+ * does not zero it. *d_count (device int64, 8-byte aligned) = the number of set bits.
+ * Errors: hj_pair_predicate_check's run first (so an invalid predicate is HJ_ERR_INVALID on
+ * a machine without a GPU too); then no GPU: HJ_ERR_NO_DEVICE; n outside [0, 2^40), a null
+ * or misaligned out_bitmap (n > 0) or d_count, null pairs (n > 0), host pointers:
+ * HJ_ERR_INVALID. One launch. Replaces the mask of apply_join_filter_to_indices
+ * (src/shared/datafusion_private.rs:295-328). */
+hj_status hj_pair_filter_test(const hj_pair_predicate* p, const uint64_t* build_idx,
+                              const uint32_t* probe_idx, int64_t n, uint8_t* out_bitmap,
+                              int64_t* d_count, void* stream);
+
+/* The passing pairs, in their input order, to out_build / out_probe (capacity n);
+ * *d_count (device int64, 8-byte aligned) = their number. Nothing at or beyond index
+ * *d_count is written. The outputs must not overlap the inputs. workspace: device, 8-byte
+ * aligned, hj_pair_filter_workspace_bytes(n) bytes (one bit per pair for the result bitmap
+ * plus 8 bytes per tile of 4096 pairs; new), not shared by concurrent calls. Evaluate, scan
+ * of the tile totals, compaction: no workgroup waits on another. Errors as
+ * hj_pair_filter_test, in the same order; a null or misaligned out_build (8 bytes) /
+ * out_probe (4 bytes) with n > 0, a null or misaligned workspace or d_count, overlapping
+ * inputs and outputs: HJ_ERR_INVALID. Replaces apply_join_filter_to_indices
+ * (src/shared/datafusion_private.rs:295-328). */
+int64_t hj_pair_filter_workspace_bytes(int64_t n);
+hj_status hj_pair_filter_select(const hj_pair_predicate* p, const uint64_t* build_idx,
+                                const uint32_t* probe_idx, int64_t n, uint64_t* out_build,
+                                uint32_t* out_probe, int64_t* d_count, void* workspace, void* stream);
+
 /* ---- multi-process, one GPU per process: RCCL behind the ABI --------------------
  * The reference runs one process; a node of GPUs driven as one process per GPU (the
  * Rust host launching a rank per device) needs the exchange steps of the multi-GPU plans
