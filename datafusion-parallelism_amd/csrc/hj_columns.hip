@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "hj_compact.h"
 #include "hj_launch.h"
 #include "hj_util.h"
 
@@ -97,21 +98,17 @@ select_write_kernel(const uint8_t* __restrict__ flags, int64_t n, uint8_t want,
         if ((i0 + k < n) && (f[k] == want)) out[pos++] = (uint64_t)(i0 + k);
 }
 
-int64_t select_workspace(int64_t n) {
-    const int64_t nt = (n + kSelTile - 1) / kSelTile;
-    return 8 * (nt + 2) + scan_scratch_bytes(nt) + 256;
-}
+int64_t select_workspace(int64_t n) { return compact_ws_bytes((n + kSelTile - 1) / kSelTile, 0); }
 
 hipError_t launch_select_rows(const uint8_t* flags, int64_t n, uint8_t want, uint64_t* out, int64_t* d_count,
                               void* workspace, hipStream_t s) {
     const int64_t nt = (n + kSelTile - 1) / kSelTile;
     if (nt == 0) return hipMemsetAsync(d_count, 0, 8, s);
-    unsigned long long* tcnt = (unsigned long long*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
-    void* scratch = tcnt + (nt + 2);
-    select_count_kernel<<<(unsigned)nt, kSelThreads, 0, s>>>(flags, n, want, tcnt);
-    hipError_t e = launch_scan_u64(tcnt, nt, scratch, (unsigned long long*)d_count, s);
+    const CompactWs w = compact_ws_carve(workspace, nt, 0);
+    select_count_kernel<<<(unsigned)nt, kSelThreads, 0, s>>>(flags, n, want, w.tcnt);
+    hipError_t e = compact_scan(w, nt, d_count, s);
     if (e != hipSuccess) return e;
-    select_write_kernel<<<(unsigned)nt, kSelThreads, 0, s>>>(flags, n, want, tcnt, out);
+    select_write_kernel<<<(unsigned)nt, kSelThreads, 0, s>>>(flags, n, want, w.tcnt, out);
     return hipGetLastError();
 }
 
@@ -176,21 +173,17 @@ static int64_t select_bitmap_tiles(int64_t n) {
     return (nwords + kSbThreads - 1) / kSbThreads;
 }
 
-int64_t select_bitmap_workspace(int64_t n) {
-    const int64_t nt = select_bitmap_tiles(n);
-    return ((8 * (nt + 2) + scan_scratch_bytes(nt) + 256 + 7) / 8) * 8;
-}
+int64_t select_bitmap_workspace(int64_t n) { return compact_ws_bytes(select_bitmap_tiles(n), 0); }
 
 hipError_t launch_select_bitmap(const uint8_t* bitmap, int64_t bit_offset, int64_t n, int want, uint32_t base,
                                 uint32_t* out, int64_t* d_count, void* workspace, hipStream_t s) {
     const int64_t nt = select_bitmap_tiles(n);
     if (nt == 0) return hipMemsetAsync(d_count, 0, 8, s);
-    unsigned long long* tcnt = (unsigned long long*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
-    void* scratch = tcnt + (nt + 2);
-    select_bitmap_count_kernel<<<(unsigned)nt, kSbThreads, 0, s>>>(bitmap, bit_offset, n, want != 0, tcnt);
-    hipError_t e = launch_scan_u64(tcnt, nt, scratch, (unsigned long long*)d_count, s);
+    const CompactWs w = compact_ws_carve(workspace, nt, 0);
+    select_bitmap_count_kernel<<<(unsigned)nt, kSbThreads, 0, s>>>(bitmap, bit_offset, n, want != 0, w.tcnt);
+    hipError_t e = compact_scan(w, nt, d_count, s);
     if (e != hipSuccess) return e;
-    select_bitmap_write_kernel<<<(unsigned)nt, kSbThreads, 0, s>>>(bitmap, bit_offset, n, want != 0, base, tcnt, out);
+    select_bitmap_write_kernel<<<(unsigned)nt, kSbThreads, 0, s>>>(bitmap, bit_offset, n, want != 0, base, w.tcnt, out);
     return hipGetLastError();
 }
 

@@ -11,7 +11,7 @@
 //                          8-byte word of the Arrow bitmap
 //   filter_select_*        ordered compaction of the passing rows (keys + u32 ids): count
 //                          per 4096-row tile (the ballots kept in the workspace), scan,
-//                          write - the shape of select_count_kernel / select_write_kernel
+//                          write - the shared compaction of hj_compact.h
 //
 // All streaming work bound by the key reads; the filter words are a gather.
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@
 
 #include <algorithm>
 
+#include "hj_compact.h"
 #include "hj_launch.h"
 #include "hj_util.h"
 
@@ -137,14 +138,13 @@ hipError_t launch_filter_add(const FilterView& f, int key_bytes, const void* key
 // ---------------------------------------------------------------------------
 // test: Arrow bitmap of the rows that are valid and present, and their number
 // ---------------------------------------------------------------------------
-constexpr int kTestThreads = 256;
+constexpr int kTestThreads = kCwThreads;  // block_count_sum's workgroup
 constexpr int kTestSteps = 4;  // key loads in flight per lane
 
 template <typename K, bool HAS_VALID, bool RANGE>
 __global__ void __launch_bounds__(kTestThreads)
 filter_test_kernel(FilterView f, const K* __restrict__ keys, const uint8_t* __restrict__ valid, int64_t voff, int64_t n,
                    unsigned long long* __restrict__ out, unsigned long long* __restrict__ d_count) {
-    __shared__ unsigned int s_c[kTestThreads / 64];
     const int lane = threadIdx.x & 63;
     unsigned int cnt = 0;  // lane 0 of each wave counts its words' bits
     const int64_t span = (int64_t)kTestThreads * kTestSteps;
@@ -167,14 +167,8 @@ filter_test_kernel(FilterView f, const K* __restrict__ keys, const uint8_t* __re
             }
         }
     }
-    if (lane == 0) s_c[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-#pragma unroll
-        for (int w = 0; w < kTestThreads / 64; ++w) t += s_c[w];
-        if (t != 0) atomicAdd(d_count, t);
-    }
+    const unsigned long long t = block_count_sum(cnt);
+    if (threadIdx.x == 0 && t != 0) atomicAdd(d_count, t);
 }
 
 template <typename K, bool HAS_VALID, bool RANGE>
@@ -196,112 +190,79 @@ hipError_t launch_filter_test(const FilterView& f, int key_bytes, const void* ke
 // ---------------------------------------------------------------------------
 // select: the passing rows' keys and ids probe_base + row, in row order
 // ---------------------------------------------------------------------------
-constexpr int kFselThreads = 256;
-constexpr int kFselWords = 64;                 // ballot words (of 64 rows) per tile
-constexpr int kFselTile = kFselWords * 64;     // 4096 rows
-constexpr int kFselSteps = kFselWords / (kFselThreads / 64);
+static_assert(kCwSteps % 4 == 0, "the count kernel loads keys in batches of four steps");
 
 // pass 1: word j of tile t covers rows t * 4096 + j * 64 ..; ballots[t * 64 + j], tcnt[t]
 template <typename K, bool HAS_VALID, bool RANGE>
-__global__ void __launch_bounds__(kFselThreads)
+__global__ void __launch_bounds__(kCwThreads)
 filter_select_count_kernel(FilterView f, const K* __restrict__ keys, const uint8_t* __restrict__ valid, int64_t voff,
                            int64_t n, unsigned long long* __restrict__ ballots, unsigned long long* __restrict__ tcnt) {
-    __shared__ unsigned int s_c[kFselThreads / 64];
     const int lane = threadIdx.x & 63;
-    const int64_t tile0 = (int64_t)blockIdx.x * kFselTile;
+    const int64_t tile0 = (int64_t)blockIdx.x * kCwTile;
     unsigned int cnt = 0;
 #pragma unroll 1
-    for (int s0 = 0; s0 < kFselSteps; s0 += 4) {
+    for (int s0 = 0; s0 < kCwSteps; s0 += 4) {
         K k[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int64_t row = tile0 + (int64_t)(s0 + u) * kFselThreads + threadIdx.x;
+            const int64_t row = tile0 + (int64_t)(s0 + u) * kCwThreads + threadIdx.x;
             k[u] = row < n ? keys[row] : (K)0;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int64_t row = tile0 + (int64_t)(s0 + u) * kFselThreads + threadIdx.x;
+            const int64_t row = tile0 + (int64_t)(s0 + u) * kCwThreads + threadIdx.x;
             const bool ok = row < n && (!HAS_VALID || bit_valid(valid, voff, row)) && filter_has<RANGE>(f, (int64_t)k[u]);
             const unsigned long long b = __ballot(ok);
             if (lane == 0) {
-                ballots[(int64_t)blockIdx.x * kFselWords + (s0 + u) * (kFselThreads / 64) + (threadIdx.x >> 6)] = b;
+                ballots[(int64_t)blockIdx.x * kCwWords + (s0 + u) * kCwWaves + (threadIdx.x >> 6)] = b;
                 cnt += (unsigned int)__popcll(b);
             }
         }
     }
-    if (lane == 0) s_c[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-#pragma unroll
-        for (int w = 0; w < kFselThreads / 64; ++w) t += s_c[w];
-        tcnt[blockIdx.x] = t;
-    }
+    const unsigned long long t = block_count_sum(cnt);
+    if (threadIdx.x == 0) tcnt[blockIdx.x] = t;
 }
 
 // pass 2: toff = the scanned tile counts; out_keys / out_ids hold `n` elements and the
 // positions are < the total <= n
 template <typename K>
-__global__ void __launch_bounds__(kFselThreads)
+__global__ void __launch_bounds__(kCwThreads)
 filter_select_write_kernel(const K* __restrict__ keys, int64_t n, uint32_t probe_base,
                            const unsigned long long* __restrict__ ballots, const unsigned long long* __restrict__ toff,
                            K* __restrict__ out_keys, uint32_t* __restrict__ out_ids) {
-    __shared__ unsigned long long s_b[kFselWords];
-    __shared__ unsigned int s_off[kFselWords];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (wave == 0) {
-        const unsigned long long b = ballots[(int64_t)blockIdx.x * kFselWords + lane];
-        const unsigned int c = (unsigned int)__popcll(b);
-        s_b[lane] = b;
-        s_off[lane] = wave_incl_scan(c) - c;
-    }
-    __syncthreads();
-    const unsigned long long t0 = toff[blockIdx.x];
-    const int64_t tile0 = (int64_t)blockIdx.x * kFselTile;
-    for (int j = wave; j < kFselWords; j += kFselThreads / 64) {
-        const unsigned long long b = s_b[j];
-        if (b == 0) continue;
-        if ((b >> lane) & 1) {
-            const int64_t row = tile0 + (int64_t)j * 64 + lane;  // < n: pass 1 sets no bit past n
-            const unsigned long long pos = t0 + s_off[j] + (unsigned int)__popcll(b & ((1ull << lane) - 1));
-            out_keys[pos] = keys[row];
-            out_ids[pos] = probe_base + (uint32_t)row;
-        }
-    }
+    // a set bit names a row < n: pass 1 sets no bit past n
+    compact_words_tile(ballots + (int64_t)blockIdx.x * kCwWords, toff[blockIdx.x], (int64_t)blockIdx.x * kCwTile,
+                       [&](int64_t row, unsigned long long pos) {
+                           out_keys[pos] = keys[row];
+                           out_ids[pos] = probe_base + (uint32_t)row;
+                       });
 }
 
-static int64_t fsel_tiles(int64_t n) { return (n + kFselTile - 1) / kFselTile; }
-
-int64_t filter_select_workspace(int64_t n) {
-    const int64_t nt = fsel_tiles(n);
-    return 8 * (nt + 2) + 8 * nt * kFselWords + scan_scratch_bytes(nt) + 256;
-}
+int64_t filter_select_workspace(int64_t n) { return compact_ws_bytes(compact_tiles(n), kCwWords); }
 
 template <typename K, bool HAS_VALID, bool RANGE>
 static void select_dispatch(const FilterView& f, const void* keys, const uint8_t* valid, int64_t voff, int64_t n,
                             int64_t nt, unsigned long long* ballots, unsigned long long* tcnt, hipStream_t s) {
-    filter_select_count_kernel<K, HAS_VALID, RANGE><<<(unsigned)nt, kFselThreads, 0, s>>>(f, (const K*)keys, valid, voff,
+    filter_select_count_kernel<K, HAS_VALID, RANGE><<<(unsigned)nt, kCwThreads, 0, s>>>(f, (const K*)keys, valid, voff,
                                                                                       n, ballots, tcnt);
 }
 
 hipError_t launch_filter_select(const FilterView& f, int key_bytes, const void* keys, const uint8_t* valid,
                                 int64_t voff, int64_t n, uint32_t probe_base, void* out_keys, uint32_t* out_ids,
                                 int64_t* d_count, void* workspace, hipStream_t s) {
-    const int64_t nt = fsel_tiles(n);
+    const int64_t nt = compact_tiles(n);
     if (nt == 0) return hipMemsetAsync(d_count, 0, 8, s);
-    unsigned long long* tcnt = (unsigned long long*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
-    unsigned long long* ballots = tcnt + (nt + 2);
-    void* scratch = ballots + nt * kFselWords;
-    DFP_FILTER_DISPATCH(select_dispatch, f, keys, valid, voff, n, nt, ballots, tcnt, s);
+    const CompactWs w = compact_ws_carve(workspace, nt, kCwWords);
+    DFP_FILTER_DISPATCH(select_dispatch, f, keys, valid, voff, n, nt, w.words, w.tcnt, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if ((e = launch_scan_u64(tcnt, nt, scratch, (unsigned long long*)d_count, s)) != hipSuccess) return e;
+    if ((e = compact_scan(w, nt, d_count, s)) != hipSuccess) return e;
     if (key_bytes == 8)
-        filter_select_write_kernel<int64_t><<<(unsigned)nt, kFselThreads, 0, s>>>(
-            (const int64_t*)keys, n, probe_base, ballots, tcnt, (int64_t*)out_keys, out_ids);
+        filter_select_write_kernel<int64_t><<<(unsigned)nt, kCwThreads, 0, s>>>(
+            (const int64_t*)keys, n, probe_base, w.words, w.tcnt, (int64_t*)out_keys, out_ids);
     else
-        filter_select_write_kernel<int32_t><<<(unsigned)nt, kFselThreads, 0, s>>>(
-            (const int32_t*)keys, n, probe_base, ballots, tcnt, (int32_t*)out_keys, out_ids);
+        filter_select_write_kernel<int32_t><<<(unsigned)nt, kCwThreads, 0, s>>>(
+            (const int32_t*)keys, n, probe_base, w.words, w.tcnt, (int32_t*)out_keys, out_ids);
     return hipGetLastError();
 }
 

@@ -11,8 +11,8 @@
 //   equal_pairs_kernel      equal_rows_arr (src/shared/datafusion_private.rs:40-80): a
 //                           candidate pair survives when its key tuples are equal in every
 //                           column (byte-exact; arrow's eq on floats is total-order, i.e.
-//                           equal bits), then the survivors are compacted in order
-//                           (select + gather), so the pairs stay canonical.
+//                           equal bits) and is a bit of its wave's ballot word; the pair
+//                           filter's ordered write (launch_compact_pairs) keeps the order.
 //
 // Columns: fixed width 1/2/4/8/16 bytes, or variable width (Utf8 / Binary with i32 or i64
 // offsets). HBM-bound streaming work; byte loads for unaligned or variable-width values.
@@ -21,6 +21,7 @@
 
 #include <algorithm>
 
+#include "hj_compact.h"
 #include "hj_device.h"
 #include "hj_launch.h"
 #include "hj_util.h"
@@ -119,22 +120,27 @@ __device__ __forceinline__ bool tuples_equal(const KeyCols& bc, const KeyCols& p
     return true;
 }
 
-__global__ void __launch_bounds__(256)
+// One pair per lane, whole waves: lane 0 stores the wave's ballot word, every word of every
+// tile (zero past n), so the compaction reads no unwritten word; ttot[tile] = equal pairs.
+__global__ void __launch_bounds__(kCwThreads)
 equal_pairs_kernel(KeyCols bc, KeyCols pc, const uint64_t* __restrict__ bidx, const uint32_t* __restrict__ pidx,
-                   int64_t n, uint8_t* __restrict__ flags) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        flags[i] = tuples_equal(bc, pc, bidx[i], pidx[i]) ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(256)
-gather_pairs_kernel(const uint64_t* __restrict__ pos, const int64_t* __restrict__ d_count,
-                    const uint64_t* __restrict__ bidx, const uint32_t* __restrict__ pidx, int64_t n,
-                    uint64_t* __restrict__ out_b, uint32_t* __restrict__ out_p) {
-    const int64_t m = *d_count;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n && i < m; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t j = pos[i];
-        out_b[i] = bidx[j];
-        out_p[i] = pidx[j];
+                   int64_t n, int64_t ntiles, unsigned long long* __restrict__ words,
+                   unsigned long long* __restrict__ ttot) {
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        unsigned int cnt = 0;
+#pragma unroll 1
+        for (int s0 = 0; s0 < kCwSteps; ++s0) {
+            const int64_t i = tile * kCwTile + (int64_t)s0 * kCwThreads + threadIdx.x;
+            const bool pass = i < n && tuples_equal(bc, pc, bidx[i], pidx[i]);  // per-lane byte loops
+            const unsigned long long word = __ballot(pass);  // after them: EXEC is full here
+            if ((threadIdx.x & 63) == 0) {
+                words[i >> 6] = word;
+                cnt += (unsigned int)__popcll(word);
+            }
+        }
+        const unsigned long long t = block_count_sum(cnt);
+        if (threadIdx.x == 0) ttot[tile] = t;
+        __syncthreads();
     }
 }
 
@@ -146,26 +152,19 @@ hipError_t launch_composite_keys(const KeyCols& cols, int64_t n, int64_t* out_ke
     return hipGetLastError();
 }
 
-int64_t equal_pairs_workspace(int64_t n) {
-    const int64_t a = (n + 255) & ~(int64_t)255;
-    return a + 8 * a + select_workspace(n) + 512;
-}
+int64_t equal_pairs_workspace(int64_t n) { return compact_ws_bytes(compact_tiles(n), kCwWords); }
 
 hipError_t launch_equal_pairs(const KeyCols& bc, const KeyCols& pc, const uint64_t* bidx, const uint32_t* pidx,
                               int64_t n, uint64_t* out_b, uint32_t* out_p, int64_t* d_count, void* ws,
                               hipStream_t s) {
-    if (n <= 0) return hipMemsetAsync(d_count, 0, sizeof(int64_t), s);
-    const int64_t a = (n + 255) & ~(int64_t)255;
-    uint8_t* base = reinterpret_cast<uint8_t*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    uint8_t* flags = base;
-    uint64_t* pos = reinterpret_cast<uint64_t*>(base + a);
-    void* sws = base + 9 * a;
-    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
-    equal_pairs_kernel<<<grid, 256, 0, s>>>(bc, pc, bidx, pidx, n, flags);
-    hipError_t e = launch_select_rows(flags, n, 1, pos, d_count, sws, s);
+    const int64_t nt = compact_tiles(n);
+    if (nt == 0) return hipMemsetAsync(d_count, 0, 8, s);
+    const CompactWs w = compact_ws_carve(ws, nt, kCwWords);
+    const unsigned grid = (unsigned)std::min<int64_t>(nt, 4096);  // grid-stride over the tiles beyond this
+    equal_pairs_kernel<<<grid, kCwThreads, 0, s>>>(bc, pc, bidx, pidx, n, nt, w.words, w.tcnt);
+    const hipError_t e = compact_scan(w, nt, d_count, s);
     if (e != hipSuccess) return e;
-    gather_pairs_kernel<<<grid, 256, 0, s>>>(pos, d_count, bidx, pidx, n, out_b, out_p);
-    return hipGetLastError();
+    return launch_compact_pairs(bidx, pidx, nt, w.words, w.tcnt, out_b, out_p, s);
 }
 
 }  // namespace dfp

@@ -290,6 +290,11 @@ int64_t pair_filter_workspace(int64_t n);
 hipError_t launch_pair_filter_select(const PairPred& pr, const uint64_t* bidx, const uint32_t* pidx, int64_t n,
                                      uint64_t* out_b, uint32_t* out_p, int64_t* d_count, void* workspace,
                                      hipStream_t s);
+// the ordered write alone (also hj_keys.hip's): words and toff of nt tiles as hj_compact.h's
+// compact_words_tile takes them
+hipError_t launch_compact_pairs(const uint64_t* bidx, const uint32_t* pidx, int64_t nt,
+                                const unsigned long long* words, const unsigned long long* toff, uint64_t* out_b,
+                                uint32_t* out_p, hipStream_t s);
 
 // ---- generators ----------------------------------------------------------
 hipError_t launch_gen_perm(int64_t* out, int64_t n, int64_t mul, int64_t range, hipStream_t s);

@@ -11,9 +11,8 @@
 //                         them are scalar branches; only the operand gathers and the BYTES
 //                         compare loop are per lane. BYTES = false leaves that loop out.
 //   pair_compact_kernel   per tile of 4096 pairs: re-reads the tile's 64 ballot words and
-//                         writes each passing pair at tile offset (scanned tile totals) +
-//                         word offset (wave scan of the popcounts) + bit rank. No workgroup
-//                         waits on another.
+//                         writes each passing pair at its rank (compact_words_tile of
+//                         hj_compact.h). No workgroup waits on another.
 //
 // HBM-bound: 12 bytes of pair read per candidate, the operand gathers, one bit written.
 #include <hip/hip_runtime.h>
@@ -21,18 +20,14 @@
 
 #include <algorithm>
 
+#include "hj_compact.h"
 #include "hj_device.h"
 #include "hj_launch.h"
 #include "hj_util.h"
 
 namespace dfp {
 
-constexpr int kPfThreads = 256;
-constexpr int kPfWaves = kPfThreads / 64;
-constexpr int kPfWords = 64;                // ballot words (of 64 pairs) per tile
-constexpr int kPfTile = kPfWords * 64;      // 4096 pairs
-constexpr int kPfSteps = kPfWords / kPfWaves;
-constexpr unsigned kPfMaxGrid = 4096;       // grid-stride over the tiles beyond this
+constexpr unsigned kPfMaxGrid = 4096;  // grid-stride over the tiles beyond this
 
 // One fixed-width operand as 64 bits, sign- (INT) or zero-extended; the column is
 // wave-uniform, so the width switch and the alignment test are scalar branches.
@@ -153,19 +148,18 @@ __device__ __forceinline__ bool pf_pair_passes(const PairPred& pr, bool live, ui
 // stored (test: ceil(n / 64); select: every word of every tile). ttot (select): the tile's
 // passing pairs; d_count (test): += the block's passing pairs, zeroed by the launcher.
 template <bool BYTES>
-__global__ void __launch_bounds__(kPfThreads)
+__global__ void __launch_bounds__(kCwThreads)
 pair_eval_kernel(PairPred pr, const uint64_t* __restrict__ bidx, const uint32_t* __restrict__ pidx, int64_t n,
                  int64_t ntiles, unsigned long long* __restrict__ words, int64_t nwords,
                  unsigned long long* __restrict__ ttot, unsigned long long* __restrict__ d_count) {
-    __shared__ unsigned int s_c[kPfWaves];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     unsigned long long block_cnt = 0;  // thread 0's
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t tile0 = tile * kPfTile;
+        const int64_t tile0 = tile * kCwTile;
         unsigned int cnt = 0;
 #pragma unroll 1
-        for (int s0 = 0; s0 < kPfSteps; ++s0) {
-            const int64_t i = tile0 + (int64_t)s0 * kPfThreads + threadIdx.x;
+        for (int s0 = 0; s0 < kCwSteps; ++s0) {
+            const int64_t i = tile0 + (int64_t)s0 * kCwThreads + threadIdx.x;
             const bool live = i < n;
             uint64_t b = 0;
             uint32_t p = 0;
@@ -181,15 +175,9 @@ pair_eval_kernel(PairPred pr, const uint64_t* __restrict__ bidx, const uint32_t*
                 cnt += (unsigned int)__popcll(word);
             }
         }
-        if (lane == 0) s_c[wave] = cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long t = 0;
-#pragma unroll
-            for (int k = 0; k < kPfWaves; ++k) t += s_c[k];
-            if (ttot != nullptr) ttot[tile] = t;
-            block_cnt += t;
-        }
+        const unsigned long long t = block_count_sum(cnt);  // thread 0's, else 0
+        if (threadIdx.x == 0 && ttot != nullptr) ttot[tile] = t;
+        block_cnt += t;
         __syncthreads();
     }
     if (threadIdx.x == 0 && d_count != nullptr && block_cnt != 0) atomicAdd(d_count, block_cnt);
@@ -197,37 +185,24 @@ pair_eval_kernel(PairPred pr, const uint64_t* __restrict__ bidx, const uint32_t*
 
 // toff: the scanned tile totals; out_b / out_p hold n elements and every position is below
 // the total <= n; a set bit names a pair < n (the evaluate kernel sets none past n)
-__global__ void __launch_bounds__(kPfThreads)
+__global__ void __launch_bounds__(kCwThreads)
 pair_compact_kernel(const uint64_t* __restrict__ bidx, const uint32_t* __restrict__ pidx, int64_t ntiles,
                     const unsigned long long* __restrict__ words, const unsigned long long* __restrict__ toff,
                     uint64_t* __restrict__ out_b, uint32_t* __restrict__ out_p) {
-    __shared__ unsigned long long s_b[kPfWords];
-    __shared__ unsigned int s_off[kPfWords];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        if (wave == 0) {
-            const unsigned long long w = words[tile * kPfWords + lane];
-            const unsigned int c = (unsigned int)__popcll(w);
-            s_b[lane] = w;
-            s_off[lane] = wave_incl_scan(c) - c;
-        }
-        __syncthreads();
-        const unsigned long long t0 = toff[tile];
-        const int64_t tile0 = tile * kPfTile;
-        for (int j = wave; j < kPfWords; j += kPfWaves) {
-            const unsigned long long w = s_b[j];
-            if ((w >> lane) & 1) {
-                const int64_t i = tile0 + (int64_t)j * 64 + lane;
-                const unsigned long long pos = t0 + s_off[j] + (unsigned int)__popcll(w & ((1ull << lane) - 1));
-                out_b[pos] = bidx[i];
-                out_p[pos] = pidx[i];
-            }
-        }
-        __syncthreads();
-    }
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x)
+        compact_words_tile(words + tile * kCwWords, toff[tile], tile * kCwTile, [&](int64_t i, unsigned long long pos) {
+            out_b[pos] = bidx[i];
+            out_p[pos] = pidx[i];
+        });
 }
 
-static int64_t pf_tiles(int64_t n) { return (n + kPfTile - 1) / kPfTile; }
+hipError_t launch_compact_pairs(const uint64_t* bidx, const uint32_t* pidx, int64_t nt,
+                                const unsigned long long* words, const unsigned long long* toff, uint64_t* out_b,
+                                uint32_t* out_p, hipStream_t s) {
+    const unsigned grid = (unsigned)std::min<int64_t>(nt, (int64_t)kPfMaxGrid * 16);
+    pair_compact_kernel<<<grid, kCwThreads, 0, s>>>(bidx, pidx, nt, words, toff, out_b, out_p);
+    return hipGetLastError();
+}
 
 static bool pf_has_bytes(const PairPred& pr) {
     for (int t = 0; t < pr.nterms; ++t)
@@ -240,9 +215,9 @@ static hipError_t pf_eval(const PairPred& pr, const uint64_t* bidx, const uint32
                           unsigned long long* d_count, hipStream_t s) {
     const unsigned grid = (unsigned)std::min<int64_t>(nt, kPfMaxGrid);
     if (pf_has_bytes(pr))
-        pair_eval_kernel<true><<<grid, kPfThreads, 0, s>>>(pr, bidx, pidx, n, nt, words, nwords, ttot, d_count);
+        pair_eval_kernel<true><<<grid, kCwThreads, 0, s>>>(pr, bidx, pidx, n, nt, words, nwords, ttot, d_count);
     else
-        pair_eval_kernel<false><<<grid, kPfThreads, 0, s>>>(pr, bidx, pidx, n, nt, words, nwords, ttot, d_count);
+        pair_eval_kernel<false><<<grid, kCwThreads, 0, s>>>(pr, bidx, pidx, n, nt, words, nwords, ttot, d_count);
     return hipGetLastError();
 }
 
@@ -250,30 +225,23 @@ hipError_t launch_pair_filter_test(const PairPred& pr, const uint64_t* bidx, con
                                    uint8_t* out_bitmap, int64_t* d_count, hipStream_t s) {
     hipError_t e = hipMemsetAsync(d_count, 0, 8, s);
     if (e != hipSuccess || n <= 0) return e;
-    return pf_eval(pr, bidx, pidx, n, pf_tiles(n), (unsigned long long*)out_bitmap, (n + 63) / 64, nullptr,
+    return pf_eval(pr, bidx, pidx, n, compact_tiles(n), (unsigned long long*)out_bitmap, (n + 63) / 64, nullptr,
                    (unsigned long long*)d_count, s);
 }
 
 // tile totals u64[nt + 2], ballot words u64[64 nt], the scan's scratch: about one bit per pair
-int64_t pair_filter_workspace(int64_t n) {
-    const int64_t nt = pf_tiles(n);
-    return 8 * (nt + 2) + 8 * nt * kPfWords + scan_scratch_bytes(nt) + 64;
-}
+int64_t pair_filter_workspace(int64_t n) { return compact_ws_bytes(compact_tiles(n), kCwWords); }
 
 hipError_t launch_pair_filter_select(const PairPred& pr, const uint64_t* bidx, const uint32_t* pidx, int64_t n,
                                      uint64_t* out_b, uint32_t* out_p, int64_t* d_count, void* workspace,
                                      hipStream_t s) {
-    const int64_t nt = pf_tiles(n);
+    const int64_t nt = compact_tiles(n);
     if (nt == 0) return hipMemsetAsync(d_count, 0, 8, s);
-    unsigned long long* ttot = (unsigned long long*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
-    unsigned long long* words = ttot + (nt + 2);
-    void* scratch = words + nt * kPfWords;
-    hipError_t e = pf_eval(pr, bidx, pidx, n, nt, words, nt * kPfWords, ttot, nullptr, s);
+    const CompactWs w = compact_ws_carve(workspace, nt, kCwWords);
+    hipError_t e = pf_eval(pr, bidx, pidx, n, nt, w.words, nt * kCwWords, w.tcnt, nullptr, s);
     if (e != hipSuccess) return e;
-    if ((e = launch_scan_u64(ttot, nt, scratch, (unsigned long long*)d_count, s)) != hipSuccess) return e;
-    const unsigned grid = (unsigned)std::min<int64_t>(nt, (int64_t)kPfMaxGrid * 16);
-    pair_compact_kernel<<<grid, kPfThreads, 0, s>>>(bidx, pidx, nt, words, ttot, out_b, out_p);
-    return hipGetLastError();
+    if ((e = compact_scan(w, nt, d_count, s)) != hipSuccess) return e;
+    return launch_compact_pairs(bidx, pidx, nt, w.words, w.tcnt, out_b, out_p, s);
 }
 
 }  // namespace dfp

@@ -692,7 +692,9 @@ hj_status hj_composite_keys(int ncols, const hj_key_column* cols, int64_t n, int
  * every column, in order: out_build / out_probe (capacity n, distinct from the inputs)
  * receive them and *d_count (device int64) their number. build_cols index the build
  * side's concatenated rows, probe_cols the probe batch's rows. workspace:
- * hj_equal_pairs_workspace_bytes(n). Asynchronous on `stream`. */
+ * hj_equal_pairs_workspace_bytes(n), about one bit per pair (one ballot word per 64 pairs
+ * and the tile totals of the ordered compaction it shares with the pair filter; three
+ * launches). Asynchronous on `stream`. */
 int64_t hj_equal_pairs_workspace_bytes(int64_t n);
 hj_status hj_filter_equal_pairs(int ncols, const hj_key_column* build_cols,
                                 const hj_key_column* probe_cols, const uint64_t* build_idx,

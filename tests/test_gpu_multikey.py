@@ -99,6 +99,65 @@ def test_filter_equal_pairs_drops_unequal_candidates(dfp):
     assert fb.tolist() == [1, 3] and fp.tolist() == [0, 1]
 
 
+EDGE_ROWS = 300   # rows of either side
+EDGE_N = [0, 1, 63, 64, 65, 4095, 4096, 4097, 8193]   # around a wave's word and the tile of 4096
+EDGE_PATTERNS = ["none", "all", "alternating", "first", "last"]
+
+
+@pytest.fixture(scope="module")
+def edge_sides():
+    """(Int64, Utf8) key columns of both sides, probe row r carrying build row r's tuple: host
+    arrays for the oracle and the device columns. Strings of 0 to 39 bytes that share a long
+    prefix, so the lanes of a wave leave the byte loop at different lengths."""
+    from datafusion_parallelism_amd.columns import DeviceColumn
+
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(41)
+    x = rng.integers(-2**40, 2**40, EDGE_ROWS)
+    assert len(set(x.tolist())) == EDGE_ROWS  # distinct rows: a pair is equal only when it names one row twice
+    s = np.array([("common-prefix-of-the-key-%d" % (r % 7) + "z" * (r % 13))[:r % 40] for r in range(EDGE_ROWS)],
+                 dtype=object)
+    cols = lambda: [DeviceColumn.from_arrow(pa.array(x, type=pa.int64()), dev),
+                    DeviceColumn.from_arrow(pa.array(s, type=pa.string()), dev)]
+    return x, s, cols(), cols()
+
+
+@pytest.mark.parametrize("pattern", EDGE_PATTERNS)
+@pytest.mark.parametrize("n", EDGE_N)
+def test_filter_equal_pairs_boundary_sizes(dfp, edge_sides, n, pattern):
+    """hj_filter_equal_pairs through the C ABI at the sizes where its tiles, words and grid
+    change, over a workspace of 0xFF bytes: out_build, out_probe and the count are exactly the
+    pairs that a numpy mask over the same index arrays keeps."""
+    from datafusion_parallelism_amd import _lib
+    from datafusion_parallelism_amd.columns import _key_columns, _stream, check
+
+    L = _lib.load()
+    dev = torch.device("cuda", 0)
+    x, s, bcols, pcols = edge_sides
+    rng = np.random.default_rng(1000 * n + EDGE_PATTERNS.index(pattern))
+    want = {"none": np.zeros(n, bool), "all": np.ones(n, bool), "alternating": np.arange(n) % 2 == 0,
+            "first": np.arange(n) == 0, "last": np.arange(n) == n - 1}[pattern]
+    bidx = rng.integers(0, EDGE_ROWS, n)
+    # an equal pair names the same row on both sides; an unequal one another row, which differs
+    # in the int64 column, in the string, or in both
+    pidx = np.where(want, bidx, (bidx + rng.integers(1, EDGE_ROWS, n)) % EDGE_ROWS)
+    mask = (x[bidx] == x[pidx]) & (s[bidx] == s[pidx])
+    assert np.array_equal(mask, want)
+    b = torch.from_numpy(bidx.astype(np.int64)).to(dev)
+    p = torch.from_numpy(pidx.astype(np.int32)).to(dev)
+    ob = torch.full((max(n, 1),), -1, dtype=torch.int64, device=dev)
+    op = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+    cnt = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    ws = torch.full((L.hj_equal_pairs_workspace_bytes(n),), 0xFF, dtype=torch.uint8, device=dev)
+    check(L.hj_filter_equal_pairs(2, _key_columns(bcols), _key_columns(pcols), b.data_ptr() if n else None,
+                                  p.data_ptr() if n else None, n, ob.data_ptr(), op.data_ptr(), cnt.data_ptr(),
+                                  ws.data_ptr(), _stream(dev)))
+    m = int(cnt.item())
+    assert m == int(mask.sum())
+    assert np.array_equal(ob[:m].cpu().numpy(), bidx[mask]) and np.array_equal(op[:m].cpu().numpy(), pidx[mask])
+    assert bool((ob[m:] == -1).all()) and bool((op[m:] == -1).all())  # nothing written past the count
+
+
 def test_operator_two_key_columns(dfp, oracle_mod):
     """ParallelHashJoin with on = [(a, x), (b, y)], 2 partitions, through the reference's
     operator surface (src/operator/parallel_hash_join.rs)."""
