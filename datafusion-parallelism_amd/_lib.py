@@ -129,6 +129,7 @@ SIGNATURES = [
     ("hj_probe_async_base", I32, [P, P, P, I64, I64, U32, P, P, I64, P, P, P]),
     ("hj_probe_match_workspace_bytes", I64, [P, I64]),
     ("hj_probe_match", I32, [P, P, P, I64, I64, P, P, P, I64, P, P, P]),
+    ("hj_probe_match_filtered", I32, [P, P, P, I64, I64, ctypes.POINTER(HjPairPredicate), P, P, P, I64, P, P]),
     ("hj_pair_plan_bytes", I64, [P, I64]),
     ("hj_pair_plan", I32, [P, P, P, I64, I64, P, P, P]),
     ("hj_pair_window", I32, [P, P, I64, P, U32, I64, I64, P, P, P, P]),

@@ -27,7 +27,8 @@ ARCH = "gfx950"
 SOURCES_HIP = ["hj_kernels.hip", "hj_columns.hip", "hj_keys.hip", "hj_filter.hip", "hj_window.hip",
                "hj_pairfilter.hip"]
 SOURCES_CPP = ["hj_api.cpp", "hj_dist.cpp"]
-HEADERS = ["hj_device.h", "hj_launch.h", "hj_util.h", "hj_compact.h", "hj_host.h", "hj_comm.h"]
+HEADERS = ["hj_device.h", "hj_launch.h", "hj_util.h", "hj_compact.h", "hj_host.h", "hj_comm.h",
+           "hj_pairpred.h"]
 # test library: the product objects + the in-process thread transport for hj_comm
 # (tests/test_gpu_dist_threads.py); never part of libdfp_hj.so
 COMMTEST_LIB = os.path.join(LIBDIR, "libdfp_hj_commtest.so")

@@ -2634,6 +2634,33 @@ hj_status hj_pair_filter_select(const hj_pair_predicate* p, const uint64_t* buil
     return HJ_OK;
 }
 
+// ---- filtered match probe: the match probe over the pairs that pass a pair predicate ----
+
+hj_status hj_probe_match_filtered(const hj_table* t, const void* keys, const uint8_t* validity, int64_t validity_offset,
+                                  int64_t n, const hj_pair_predicate* pred, uint8_t* out_bitmap, uint32_t* out_counts,
+                                  uint8_t* build_flags, int64_t nflags, int64_t* d_stats, void* stream) {
+    PairPred pr;
+    hj_status st = pair_pred(pred, &pr);  // first: an invalid predicate is HJ_ERR_INVALID without a GPU too
+    if (st != HJ_OK) return st;
+    if ((st = check_table(t)) != HJ_OK) return st;
+    if (t->multi) return fail(HJ_ERR_INVALID, kMatchMulti);
+    if ((st = check_probe_args(n, 0, 0, nullptr)) != HJ_OK) return st;
+    if (n > 0 && keys == nullptr) return fail(HJ_ERR_INVALID, "null keys");
+    if (nflags < 0 || (nflags > 0 && build_flags == nullptr)) return fail(HJ_ERR_INVALID, "bad build_flags / nflags");
+    if (reinterpret_cast<uintptr_t>(out_bitmap) & 7) return fail(HJ_ERR_INVALID, "out_bitmap must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(out_counts) & 3) || (reinterpret_cast<uintptr_t>(d_stats) & 7))
+        return fail(HJ_ERR_INVALID, "out_counts must be 4-byte and d_stats 8-byte aligned");
+    if (pr.probe_rows < n)
+        return fail(HJ_ERR_INVALID, "hj_probe_match_filtered: the predicate's probe_rows is below n (row i of the "
+                                    "probe columns belongs to key i)");
+    HIP_TRY(hipSetDevice(t->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((st = wait_built(t, s)) != HJ_OK) return st;  // the probe orders itself after the build
+    HIP_TRY(launch_probe_match_filtered(t->key_bytes, view_of(t), pr, keys, validity, validity_offset, n, out_bitmap,
+                                        out_counts, build_flags, nflags, d_stats, s));
+    return note_probe(t, s);  // hj_table_free waits for it
+}
+
 hj_status hj_gen_perm_keys(int64_t* out, int64_t n, int64_t mul, int64_t range, void* stream) {
     if (device_count() == 0) return fail(HJ_ERR_NO_DEVICE, "no GPU visible");
     if (range <= 0 || n < 0) return fail(HJ_ERR_INVALID, "bad range");

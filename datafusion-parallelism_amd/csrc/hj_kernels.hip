@@ -36,6 +36,7 @@
 
 #include "hj_device.h"
 #include "hj_launch.h"
+#include "hj_pairpred.h"
 #include "hj_util.h"
 
 namespace dfp {
@@ -5206,6 +5207,213 @@ hipError_t launch_probe_match(int key_bytes, const TableView& tv, const void* ke
     }
 #undef DFP_MATCH_K
 #undef DFP_MATCH
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// filtered match probe: the match probe's outputs over F, the pairs of the probe that pass
+// a pair predicate, in place of all its pairs S. What the reference's semi and anti joins
+// keep once apply_join_filter_to_indices (src/shared/datafusion_private.rs:295-328) has
+// dropped the failing pairs and get_semi_indices / set_ones have folded the rest into flags
+// (right_semi.rs:74-125, left_semi.rs:112-164; the filter runs before any marking,
+// full.rs:140-175). The skeleton is probe_match_kernel's: lookup4, four ballots per bitmap
+// word, one atomic per workgroup and statistic. Between the lookup and the outputs every
+// matched row walks its key's build rows and evaluates the predicate (pf_pair_passes) in
+// registers: no pair is written.
+//
+// The walk. A key of <= kMatchLaneWalk rows is walked by the lane that owns the probe row
+// (a single row: one step). Larger keys are taken by the wave one after another: lane L
+// evaluates candidates L, L + 64, ... and a ballot per round gives the owner the count.
+// The four rows of a lane are taken in a rolled loop (the refs picked by selects on the
+// scalar loop counter), so the predicate's code exists twice per kernel, not eight times.
+//
+// MODE. kMfExists (no counts, no flags): a row's walk stops at its first passing pair - the
+// lane's loop by itself, the wave's rounds on the first non-zero ballot, wave-uniformly.
+// kMfFull: every candidate is evaluated, counted, and its build row marked. With flags as
+// the only output (flags_only) a candidate whose flag reads 1, or whose id the flags do not
+// cover, is skipped unevaluated: flags are only ever stored 1, so a stale 0 costs one
+// evaluation and nothing else. There is no claim bitmap: under a predicate different probe
+// rows of a key pass different build rows.
+// ---------------------------------------------------------------------------
+constexpr int kMfExists = 0, kMfFull = 1;
+
+__device__ __forceinline__ uint32_t mf_sel4(const uint32_t (&a)[4], int q) {
+    return q == 0 ? a[0] : (q == 1 ? a[1] : (q == 2 ? a[2] : a[3]));
+}
+__device__ __forceinline__ void mf_put4(uint32_t (&a)[4], int q, uint32_t v) {
+    a[0] = q == 0 ? v : a[0];
+    a[1] = q == 1 ? v : a[1];
+    a[2] = q == 2 ? v : a[2];
+    a[3] = q == 3 ? v : a[3];
+}
+
+// whether the pair (build row `row`, probe row `prow`) is in F; kMfFull marks it
+template <bool BYTES, int MODE>
+__device__ __forceinline__ bool mf_candidate(const TableView& tv, const PairPred& pr, uint32_t row, uint32_t prow,
+                                             uint8_t* flags, uint64_t nflags, bool flags_only) {
+    const uint64_t id = tv.row_ids != nullptr ? tv.row_ids[row] : (uint64_t)row;
+    if constexpr (MODE == kMfFull) {
+        if (flags_only && (id >= nflags || flags[id] != 0)) return false;  // a racy read: see above
+    }
+    const bool pass = pf_pair_passes<BYTES>(pr, true, id, prow);  // an id >= build_rows fails unread
+    if constexpr (MODE == kMfFull) {
+        if (pass && id < nflags) flags[id] = 1;  // nflags is 0 without flags
+    }
+    return pass;
+}
+
+// stat_mask: bit 0 = stats[0] is asked for, bit 1 = stats[1]; stats[2] always (stats may be null)
+template <typename K, bool HAS_VALID, bool BYTES, int MODE>
+__global__ void __launch_bounds__(kMatchThreads)
+probe_match_filtered_kernel(TableView tv, PairPred pr, const void* __restrict__ keys,
+                            const uint8_t* __restrict__ valid, int64_t voff, int64_t n, bool vec,
+                            unsigned long long* __restrict__ out_bitmap, uint32_t* __restrict__ out_counts, bool cvec,
+                            uint8_t* flags, uint64_t nflags, bool flags_only, unsigned long long* __restrict__ stats,
+                            int stat_mask) {
+    __shared__ unsigned long long s_m[kMatchThreads / 64], s_p[kMatchThreads / 64], s_c[kMatchThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t nwords = (n + 63) >> 6;
+    unsigned long long matched = 0, pairs = 0, cand = 0;
+    for (int64_t blk0 = (int64_t)blockIdx.x * kMatchRows; blk0 < n; blk0 += (int64_t)gridDim.x * kMatchRows) {
+        const int64_t wrow0 = blk0 + (int64_t)wave * 256;
+        if (wrow0 >= n) continue;  // the whole wave: no word of the bitmap starts here
+        const int64_t row0 = wrow0 + (int64_t)lane * 4;
+        uint32_t ref[4] = {kMiss, kMiss, kMiss, kMiss}, cnt[4] = {0, 0, 0, 0};
+        if (row0 < n) lookup4<K, HAS_VALID>(tv, keys, valid, voff, n, vec, row0, ref, cnt);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            cnt[q] = resolve_count(tv.dup_rows, ref[q], cnt[q], tv.off_mask);
+            cand += cnt[q];
+        }
+        // hit[q]: the row's pairs in F (kMfExists: 0 / 1)
+        uint32_t hit[4] = {0, 0, 0, 0};
+#pragma unroll 1
+        for (int q = 0; q < 4; ++q) {  // keys the owning lane walks
+            const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q);
+            uint32_t h = 0;
+            if (c != 0 && c <= kMatchLaneWalk) {  // a matched row: row0 + q < n
+                const uint32_t prow = (uint32_t)(row0 + q);
+                for (uint32_t j = 0; j < c; ++j) {
+                    const uint32_t row = (r & kDupFlag) ? dup_ref_row(tv.dup_rows, r, tv.off_mask, j) : r;
+                    if (mf_candidate<BYTES, MODE>(tv, pr, row, prow, flags, nflags, flags_only)) {
+                        ++h;
+                        if (MODE == kMfExists) break;
+                    }
+                }
+            }
+            mf_put4(hit, q, h);
+        }
+#pragma unroll 1
+        for (int q = 0; q < 4; ++q) {  // larger keys: the wave walks them one after another
+            const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q);
+            uint32_t h = mf_sel4(hit, q);
+            unsigned long long m = __ballot(c > kMatchLaneWalk);
+            while (m) {
+                const int src = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const uint32_t sr = __shfl(r, src, 64), sc = __shfl(c, src, 64);
+                const uint32_t prow = (uint32_t)(wrow0 + (int64_t)src * 4 + q);
+                uint32_t tot = 0;
+                for (uint32_t j0 = 0; j0 < sc; j0 += 64) {  // sc <= the build's rows < 2^32 - 64
+                    const uint32_t j = j0 + (uint32_t)lane;
+                    bool pass = false;
+                    if (j < sc)
+                        pass = mf_candidate<BYTES, MODE>(tv, pr, dup_ref_row(tv.dup_rows, sr, tv.off_mask, j), prow,
+                                                         flags, nflags, flags_only);
+                    const unsigned long long b = __ballot(pass);
+                    tot += (uint32_t)__popcll(b);
+                    if (MODE == kMfExists && b != 0) break;  // wave-uniform
+                }
+                if (lane == src) h = tot;
+            }
+            mf_put4(hit, q, h);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            matched += hit[q] != 0;
+            pairs += hit[q];
+        }
+        if (out_bitmap != nullptr) {
+            unsigned long long b[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) b[q] = __ballot(hit[q] != 0);
+            if (lane < 4) {  // lane w assembles word w of the wave's four
+                unsigned long long word = 0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) word |= spread16_by4(b[q] >> (16 * lane)) << q;
+                const int64_t widx = (wrow0 >> 6) + lane;
+                if (widx < nwords) out_bitmap[widx] = word;  // rows >= n have no candidate: tail bits 0
+            }
+        }
+        if constexpr (MODE == kMfFull) {
+            if (out_counts != nullptr) {
+                if (cvec && row0 + 4 <= n) {
+                    *reinterpret_cast<uint4*>(out_counts + row0) = make_uint4(hit[0], hit[1], hit[2], hit[3]);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (row0 + q < n) out_counts[row0 + q] = hit[q];
+                }
+            }
+        }
+    }
+    // statistics: wave reduction, then one atomic per workgroup and statistic
+    const unsigned long long wm = wave_sum<unsigned long long>(matched);
+    const unsigned long long wc = wave_sum<unsigned long long>(cand);
+    unsigned long long wp = 0;
+    if constexpr (MODE == kMfFull) wp = wave_sum<unsigned long long>(pairs);
+    if (lane == 0) { s_m[wave] = wm; s_p[wave] = wp; s_c[wave] = wc; }
+    __syncthreads();
+    if (threadIdx.x == 0 && stats != nullptr) {
+        unsigned long long tm = 0, tp = 0, tc = 0;
+        for (int w = 0; w < kMatchThreads / 64; ++w) { tm += s_m[w]; tp += s_p[w]; tc += s_c[w]; }
+        if (tm && (stat_mask & 1)) atomicAdd(stats, tm);
+        if (tp && (stat_mask & 2)) atomicAdd(stats + 1, tp);
+        if (tc) atomicAdd(stats + 2, tc);
+    }
+}
+
+hipError_t launch_probe_match_filtered(int key_bytes, const TableView& tv, const PairPred& pr, const void* keys,
+                                       const uint8_t* valid, int64_t voff, int64_t n, uint8_t* out_bitmap,
+                                       uint32_t* out_counts, uint8_t* flags, int64_t nflags, int64_t* d_stats,
+                                       hipStream_t s) {
+    unsigned long long* stats = reinterpret_cast<unsigned long long*>(d_stats);
+    const int stat_mask = ((out_bitmap != nullptr || out_counts != nullptr) ? 1 : 0) | (out_counts != nullptr ? 2 : 0);
+    if (stats != nullptr) {
+        hipError_t e = hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), s);
+        // the statistics nobody asked the walk for read -1: [1], or [0] and [1]
+        if (e == hipSuccess && stat_mask != 3)
+            e = hipMemsetAsync(stats + (stat_mask & 1), 0xFF, (size_t)(2 - (stat_mask & 1)) * 8, s);
+        if (e != hipSuccess) return e;
+    }
+    if (n <= 0) return hipSuccess;
+    const bool mark = flags != nullptr && nflags > 0;
+    const bool full = out_counts != nullptr || mark;
+    const bool flags_only = mark && out_bitmap == nullptr && out_counts == nullptr;
+    bool bytes = false;  // the BYTES compare loop only where a term needs it
+    for (int t = 0; t < pr.nterms; ++t) bytes = bytes || pr.t[t].cls == kPfBytes;
+    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15) == 0;
+    const bool cvec = (reinterpret_cast<uintptr_t>(out_counts) & 15) == 0;
+    const unsigned grid = (unsigned)std::min<int64_t>((n + kMatchRows - 1) / kMatchRows, kMatchMaxBlocks);
+    unsigned long long* bm = reinterpret_cast<unsigned long long*>(out_bitmap);
+#define DFP_MF(KT, HV, BY, MD)                                                                                    \
+    probe_match_filtered_kernel<KT, HV, BY, MD><<<grid, kMatchThreads, 0, s>>>(                                   \
+        tv, pr, keys, valid, voff, n, vec, bm, out_counts, cvec, mark ? flags : nullptr, mark ? (uint64_t)nflags : 0, \
+        flags_only, stats, stat_mask)
+#define DFP_MF_K(KT, HV)                                    \
+    do {                                                    \
+        if (bytes && full) DFP_MF(KT, HV, true, kMfFull);   \
+        else if (bytes) DFP_MF(KT, HV, true, kMfExists);    \
+        else if (full) DFP_MF(KT, HV, false, kMfFull);      \
+        else DFP_MF(KT, HV, false, kMfExists);              \
+    } while (0)
+    if (key_bytes == 8) {
+        if (valid) DFP_MF_K(int64_t, true); else DFP_MF_K(int64_t, false);
+    } else {
+        if (valid) DFP_MF_K(int32_t, true); else DFP_MF_K(int32_t, false);
+    }
+#undef DFP_MF_K
+#undef DFP_MF
     return hipGetLastError();
 }
 

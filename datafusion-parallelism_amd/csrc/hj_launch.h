@@ -296,6 +296,18 @@ hipError_t launch_compact_pairs(const uint64_t* bidx, const uint32_t* pidx, int6
                                 const unsigned long long* words, const unsigned long long* toff, uint64_t* out_b,
                                 uint32_t* out_p, hipStream_t s);
 
+// ---- filtered match probe (hj_kernels.hip: the match probe's lookup + the pair pass rule) ----
+// The match probe's outputs with F, the pairs of the probe that pass `pr`, in place of all its
+// pairs: out_bitmap / out_counts / flags as launch_probe_match defines them (every one
+// optional). d_stats (optional) int64[3]: [0] rows with a pair in F if a bitmap or counts are
+// asked for, else -1; [1] |F| if counts are asked for, else -1; [2] the probe's pairs. No
+// workspace, one kernel. The caller has ordered `s` after the build and checked
+// pr.probe_rows >= n.
+hipError_t launch_probe_match_filtered(int key_bytes, const TableView& tv, const PairPred& pr, const void* keys,
+                                       const uint8_t* valid, int64_t voff, int64_t n, uint8_t* out_bitmap,
+                                       uint32_t* out_counts, uint8_t* flags, int64_t nflags, int64_t* d_stats,
+                                       hipStream_t s);
+
 // ---- generators ----------------------------------------------------------
 hipError_t launch_gen_perm(int64_t* out, int64_t n, int64_t mul, int64_t range, hipStream_t s);
 hipError_t launch_gen_uniform(int64_t* out, int64_t n, uint64_t seed, int64_t range,

@@ -28,7 +28,9 @@ whose build and probe run on the gfx950 kernels through the C ABI (``include/hj.
                                                               _finalize_build_side
   apply_join_filter_to_indices (src/shared/datafusion_private.rs:295-328)
                                                               JoinFilter (host callable),
-                                                              CompareFilter (device, hj_pair_filter_select)
+                                                              CompareFilter (device, hj_pair_filter_select;
+                                                              semi / anti joins under match_probe:
+                                                              hj_probe_match_filtered, no pairs)
 
 Join keys: one Int32/Int64 column goes to the table as is (exact keys); several key
 columns, or a key of any other fixed-width or Utf8/Binary type, go through
@@ -199,8 +201,10 @@ class CompareFilter:
 
     def predicate(self, build_cols: Sequence[DeviceColumn], build_names: Sequence[str],
                   probe_cols: Sequence[DeviceColumn], probe_names: Sequence[str], build_rows: int,
-                  probe_rows: int) -> PairPredicate:
-        """The PairPredicate over the columns the terms name (each column listed once)."""
+                  probe_rows: int, eq_keys: Sequence[tuple[DeviceColumn, DeviceColumn]] = ()) -> PairPredicate:
+        """The PairPredicate over the columns the terms name (each column listed once).
+        eq_keys: (build column, probe column) pairs, one `==` term each after the filter's
+        own (the exact key equality of a composite-key match probe)."""
         lnames, rnames = self._names(L), self._names(R)
         bnames, pnames = list(build_names), list(probe_names)
 
@@ -214,9 +218,11 @@ class CompareFilter:
         for n, names, side in [(n, bnames, "build") for n in lnames] + [(n, pnames, "probe") for n in rnames]:
             if n not in names:
                 raise HjError(HJ_ERR_INVALID, f"CompareFilter: the {side} side has no column {n!r}")
-        return PairPredicate([build_cols[bnames.index(n)] for n in lnames],
-                             [probe_cols[pnames.index(n)] for n in rnames],
-                             [(ref(a), op, ref(b)) for a, op, b in self.terms], build_rows, probe_rows)
+        return PairPredicate([build_cols[bnames.index(n)] for n in lnames] + [b for b, _ in eq_keys],
+                             [probe_cols[pnames.index(n)] for n in rnames] + [p for _, p in eq_keys],
+                             [(ref(a), op, ref(b)) for a, op, b in self.terms] +
+                             [(("build", len(lnames) + i), "==", ("probe", len(rnames) + i))
+                              for i in range(len(eq_keys))], build_rows, probe_rows)
 
     def as_callable(self) -> "JoinFilter":
         """The same condition as a host JoinFilter over pyarrow compute calls (IEEE float
@@ -463,8 +469,15 @@ class BuildImplementation:
         that have no pair).
         match_probe: LeftSemi, LeftAnti, RightSemi and RightAnti probe batches ask the table
         only whether each row has a partner (HashTable.probe_match: a bitmap and the build
-        marks, no pairs) when the join has no filter, its key is one Int32/Int64 column and
-        the table lives on one device; every other case silently takes the pair path. The
+        marks, no pairs) when the table lives on one device and the join has no filter or a
+        CompareFilter - then the partner must also pass it (hj_probe_match_filtered: the walk
+        over a key's build rows and the comparisons stay in registers and stop at the first
+        passing pair). The key is one Int32/Int64 column, or a composite key of integer,
+        boolean, date / time / timestamp / duration and Utf8 / Binary columns (the same type
+        on both sides): its 64-bit hash goes to the table and one `==` term per key column
+        joins the predicate. The remaining cases silently take the pair path: a callable
+        JoinFilter, `devices=`, float / decimal key columns, and predicates beyond 16 terms
+        or 16 columns of a side. The
         output is the same. The match path does not use the key filter: with prefilter=True
         too, the filter serves only the probes that take the pair path. Off by default: the
         match path reads the table at random where the pair path's sliced probe reads it out
@@ -563,15 +576,84 @@ def _apply_filter(flt: "JoinFilter | CompareFilter", build_cols: list[DeviceColu
 _MATCH_JOINS = (JoinType.LeftSemi, JoinType.LeftAnti, JoinType.RightSemi, JoinType.RightAnti)
 
 
-def _takes_match_path(jt: JoinType, filter, lookup: GpuIndexLookup, key_cols: Sequence[DeviceColumn], n: int) -> bool:
-    """BuildImplementation(match_probe=True): a semi / anti join without a filter, keyed by
-    one Int32/Int64 column (a composite key's 64-bit hash needs the equality re-check on
-    pairs), on a one-device table."""
+def _exact_eq_key_type(t: pa.DataType) -> bool:
+    """Key column types whose pair-predicate `==` is equality of the key values: ints, uints,
+    bool, date / time / timestamp / duration, Utf8 / LargeUtf8 / Binary / LargeBinary. Not
+    floats (the totalOrder `==` of a widened float32 is not bit equality for signalling
+    NaNs) and not 16-byte columns (no term can name them)."""
+    ty = pa.types
+    return (ty.is_integer(t) or ty.is_boolean(t) or ty.is_date(t) or ty.is_time(t) or ty.is_timestamp(t)
+            or ty.is_duration(t) or t in (pa.string(), pa.large_string(), pa.binary(), pa.large_binary()))
+
+
+def _simple_match_key(lookup: GpuIndexLookup, key_cols: Sequence[DeviceColumn]) -> bool:
+    return not lookup._shared.composite and _is_simple_key(key_cols)
+
+
+def _takes_match_path(jt: JoinType, filter, lookup: GpuIndexLookup, key_cols: Sequence[DeviceColumn], n: int,
+                      build_side_records=None) -> bool:
+    """BuildImplementation(match_probe=True): a semi / anti join on a one-device table, without
+    a filter or under a CompareFilter (a callable JoinFilter needs gathered rows: the pair
+    path). Keyed by one Int32/Int64 column, or by a composite key whose every column has an
+    exact `==` term (_exact_eq_key_type, the same type on both sides): the table only holds
+    the 64-bit hashes of such keys, one `==` term per key column after the filter's own makes
+    the match exact. More than 16 terms, or 16 columns of a side, keep the pair path."""
     sh = lookup._shared
-    return (sh is not None and sh.match_probe and jt in _MATCH_JOINS and filter is None and n > 0
-            and not sh.composite and len(key_cols) == 1
-            and (pa.types.is_int64(key_cols[0].type) or pa.types.is_int32(key_cols[0].type))
-            and lookup.table.devices is None)
+    if not (sh is not None and sh.match_probe and jt in _MATCH_JOINS and n > 0 and lookup.table.devices is None):
+        return False
+    if filter is not None and not isinstance(filter, CompareFilter):
+        return False
+    if _simple_match_key(lookup, key_cols):
+        return True
+    if build_side_records is None or len(key_cols) != len(sh.key_exprs):
+        return False
+    schema = build_side_records.schema
+    for e, k in zip(sh.key_exprs, key_cols):
+        bt = schema.field(e).type
+        if bt != k.type or not _exact_eq_key_type(bt):
+            return False
+    nk = len(key_cols)
+    nt, nl, nr = (len(filter.terms), len(filter._names(L)), len(filter._names(R))) if filter is not None else (0, 0, 0)
+    return nt + nk <= 16 and nl + nk <= 16 and nr + nk <= 16
+
+
+def _match_probe(jt: JoinType, filter: "CompareFilter | None", build_side_records, lookup: GpuIndexLookup,
+                 probe_batch: pa.RecordBatch, probe_cols: list[DeviceColumn], key_cols: list[DeviceColumn],
+                 build_visited: torch.Tensor | None) -> torch.Tensor | None:
+    """The match path of one probe batch (_takes_match_path holds): no pairs. Left joins mark
+    `build_visited` (set_ones) and return None; right joins return the selected probe rows
+    (get_semi_indices / get_anti_indices) from the matched-probe bitmap. Without a filter on
+    one Int32/Int64 key: HashTable.probe_match as is. Else the filtered match probe, under the
+    predicate _apply_filter would build, plus the key equalities of a composite key."""
+    n = probe_batch.num_rows
+    left = jt in (JoinType.LeftSemi, JoinType.LeftAnti)
+    flags = build_visited if left else None
+    simple = _simple_match_key(lookup, key_cols)
+    if simple:
+        k = key_cols[0]
+        keys, valid, voff = k.key_tensor(), k.valid, k.voff
+    else:
+        (keys, valid), voff = composite_keys(key_cols), 0
+    if simple and filter is None:
+        m = lookup.table.probe_match(keys, valid, valid_offset=voff, build_flags=flags)
+    else:
+        build_cols = lookup.build_columns(build_side_records)
+        bnames, nb = list(build_side_records.schema.names), build_side_records.num_rows
+        eq = []
+        if not simple:
+            sh = lookup._shared
+            eq = [(build_cols[e if isinstance(e, int) else build_side_records.schema.get_field_index(e)], k)
+                  for e, k in zip(sh.key_exprs, key_cols)]
+        if filter is not None:
+            pred = filter.predicate(build_cols, bnames, probe_cols, list(probe_batch.schema.names), nb, n, eq_keys=eq)
+        else:
+            pred = PairPredicate([b for b, _ in eq], [p for _, p in eq],
+                                 [(("build", i), "==", ("probe", i)) for i in range(len(eq))], nb, n)
+        m = lookup.table.probe_match(keys, valid, valid_offset=voff, build_flags=flags, predicate=pred,
+                                     bitmap=not left)
+    if left:
+        return None
+    return select_bitmap(m.bitmap, n, 1 if jt is JoinType.RightSemi else 0)
 
 
 def probe_batch(join_type: JoinType, probe_expressions: Sequence[str | int], build_expressions: Sequence[str | int],
@@ -595,16 +677,12 @@ def probe_batch(join_type: JoinType, probe_expressions: Sequence[str | int], bui
     if limit is not None:
         return _probe_batch_windowed(jt, filter, build_side_records, lookup, probe_batch, probe_cols, key_cols,
                                      build_visited, limit)
-    if _takes_match_path(jt, filter, lookup, key_cols, n):
+    if _takes_match_path(jt, filter, lookup, key_cols, n, build_side_records):
         # no pairs: the matched-probe bitmap (get_semi_indices / get_anti_indices) and the
         # visited build rows (set_ones) straight from the lookup
-        k = key_cols[0]
-        left = jt in (JoinType.LeftSemi, JoinType.LeftAnti)
-        m = lookup.table.probe_match(k.key_tensor(), k.valid, valid_offset=k.voff,
-                                     build_flags=build_visited if left else None)
-        if left:
+        rows = _match_probe(jt, filter, build_side_records, lookup, probe_batch, probe_cols, key_cols, build_visited)
+        if rows is None:
             return None
-        rows = select_bitmap(m.bitmap, n, 1 if jt is JoinType.RightSemi else 0)
         return _batch([c.take(rows) for c in probe_cols], list(probe_batch.schema.names))
     b, p = lookup.matching_indices_device(key_cols, build_side_records)
     build_cols = lookup.build_columns(build_side_records)
@@ -646,14 +724,10 @@ def _probe_batch_windowed(jt: JoinType, filter: "JoinFilter | CompareFilter | No
     dev = lookup.device
     n = probe_batch.num_rows
     pnames = list(probe_batch.schema.names)
-    if _takes_match_path(jt, filter, lookup, key_cols, n):
-        k = key_cols[0]
-        left = jt in (JoinType.LeftSemi, JoinType.LeftAnti)
-        m = lookup.table.probe_match(k.key_tensor(), k.valid, valid_offset=k.voff,
-                                     build_flags=build_visited if left else None)
-        if left:
+    if _takes_match_path(jt, filter, lookup, key_cols, n, build_side_records):
+        rows = _match_probe(jt, filter, build_side_records, lookup, probe_batch, probe_cols, key_cols, build_visited)
+        if rows is None:
             return []
-        rows = select_bitmap(m.bitmap, n, 1 if jt is JoinType.RightSemi else 0)
         return [_batch([c.take(r) for c in probe_cols], pnames) for r in _row_chunks(rows, limit)]
     build_cols = lookup.build_columns(build_side_records)
     bnames = list(build_side_records.schema.names)
@@ -808,9 +882,10 @@ class ParallelHashJoin:
         not with `devices=`);
         devices / plan: one build table over several GPUs (BuildImplementation);
         prefilter: probe through a key filter over the build keys (BuildImplementation);
-        match_probe: semi and anti joins without a filter, on one Int32/Int64 key and one
-        device, probe for matches instead of pairs (BuildImplementation; same output; the
-        match path ignores the key filter; other joins silently take the pair path)."""
+        match_probe: semi and anti joins on one device, without a filter or under a
+        CompareFilter, probe for matches instead of pairs (BuildImplementation; same output;
+        the match path ignores the key filter; a callable JoinFilter, float / decimal key
+        columns and other joins silently take the pair path)."""
         if len(on) < 1:
             raise HjError(HJ_ERR_INVALID, "an equi-join needs at least one (left, right) key pair")
         self.join_type = JoinType.parse(join_type)

@@ -118,26 +118,39 @@ class MatchResult:
     """Result of HashTable.probe_match: `bitmap` (uint8 device tensor, an Arrow LSB bitmap of
     ceil(n/64)*8 bytes, bit i = row i has a partner; usable as a `valid` bitmap), `counts`
     (int32 device tensor of the rows' pair counts, the bits of a uint32; or None) and the
-    lazily read statistics `matched` and `pairs` (the only host synchronisation)."""
+    lazily read statistics `matched`, `pairs` and `candidates` (the only host
+    synchronisation). Under a predicate (hj_probe_match_filtered) bitmap, counts, matched and
+    pairs speak of the pairs that pass it, candidates of all pairs of the probe; `matched` /
+    `pairs` are None where the library computed none (-1: no bitmap or counts / no counts
+    were asked for), and `bitmap` is None when none was asked for."""
 
-    def __init__(self, n: int, bitmap: torch.Tensor, counts: torch.Tensor | None, d_stats: torch.Tensor):
+    def __init__(self, n: int, bitmap: torch.Tensor | None, counts: torch.Tensor | None, d_stats: torch.Tensor):
         self.n, self.bitmap, self.counts, self._d_stats, self._stats = n, bitmap, counts, d_stats, None
 
-    def _read(self) -> tuple[int, int]:
+    def _read(self) -> tuple:
         if self._stats is None:
-            m, p = self._d_stats.cpu().tolist()
-            self._stats = (int(m), int(p))
+            st = [int(v) for v in self._d_stats.cpu().tolist()]
+            if len(st) == 2:  # the unfiltered probe: every pair is a candidate
+                self._stats = (st[0], st[1], st[1])
+            else:
+                self._stats = (None if st[0] < 0 else st[0], None if st[1] < 0 else st[1], st[2])
         return self._stats
 
     @property
-    def matched(self) -> int:
+    def matched(self) -> int | None:
         """Probe rows with a partner (set bits of the bitmap)."""
         return self._read()[0]
 
     @property
-    def pairs(self) -> int:
-        """Pairs an inner probe of the same rows would produce (may exceed 2^32)."""
+    def pairs(self) -> int | None:
+        """Pairs an inner probe of the same rows would produce (may exceed 2^32); under a
+        predicate, those of them that pass it."""
         return self._read()[1]
+
+    @property
+    def candidates(self) -> int:
+        """Pairs of the probe before any predicate (d_stats[2]; without one: `pairs`)."""
+        return self._read()[2]
 
 
 class PairPlan:
@@ -410,23 +423,50 @@ class HashTable:
             check(_lib.HJ_ERR_INVALID, self._L)
         return v
 
-    def probe_match_async(self, keys_ptr: int, n: int, bitmap_ptr: int | None, workspace_ptr: int, stream: int = 0,
-                          valid_ptr: int | None = None, voff: int = 0, counts_ptr: int | None = None,
-                          build_flags_ptr: int | None = None, nflags: int = 0, d_stats_ptr: int | None = None) -> None:
+    def probe_match_async(self, keys_ptr: int, n: int, bitmap_ptr: int | None, workspace_ptr: int | None = None,
+                          stream: int = 0, valid_ptr: int | None = None, voff: int = 0, counts_ptr: int | None = None,
+                          build_flags_ptr: int | None = None, nflags: int = 0, d_stats_ptr: int | None = None,
+                          predicate=None) -> None:
         """hj_probe_match on raw device pointers (no sync, no allocation); every output
-        pointer is optional."""
+        pointer is optional. predicate (a columns.PairPredicate): hj_probe_match_filtered
+        instead - no workspace (workspace_ptr is ignored), d_stats is an int64[3]."""
+        if predicate is not None:
+            check(self._L.hj_probe_match_filtered(self._h, keys_ptr or None, valid_ptr, voff, n, predicate.struct,
+                                                  bitmap_ptr, counts_ptr, build_flags_ptr, nflags, d_stats_ptr,
+                                                  stream or None), self._L)
+            return
         check(self._L.hj_probe_match(self._h, keys_ptr or None, valid_ptr, voff, n, bitmap_ptr, counts_ptr,
                                      build_flags_ptr, nflags, d_stats_ptr, workspace_ptr, stream or None), self._L)
 
+    def _probe_match_filtered(self, ki: KeyInput, dev, counts: bool, build_flags: torch.Tensor | None, predicate,
+                              bitmap: bool) -> "MatchResult":
+        n = ki.n
+        bm = torch.empty(((n + 63) // 64) * 8, dtype=torch.uint8, device=dev) if bitmap else None
+        cnt = torch.empty(n, dtype=torch.int32, device=dev) if counts else None
+        d_stats = torch.empty(3, dtype=torch.int64, device=dev)
+        self.probe_match_async(ki.ptr, n, None if bm is None else bm.data_ptr(), None,
+                               torch.cuda.current_stream(dev).cuda_stream, ki.valid_ptr, ki.voff,
+                               None if cnt is None else cnt.data_ptr(),
+                               None if build_flags is None else build_flags.data_ptr(),
+                               0 if build_flags is None else build_flags.numel(), d_stats.data_ptr(), predicate)
+        # the key tensors and the predicate's columns are released in stream order by torch's allocator
+        return MatchResult(n, bm, cnt, d_stats)
+
     def probe_match(self, keys: torch.Tensor, valid=None, valid_offset: int = 0, counts: bool = False,
-                    build_flags: torch.Tensor | None = None) -> "MatchResult":
+                    build_flags: torch.Tensor | None = None, predicate=None, bitmap: bool = True) -> "MatchResult":
         """Per probe row whether (and, with counts=True, how often) its key occurs in the
         table, without materialising pairs: what a semi or anti join needs. keys: a device
         tensor; valid: bool mask or LSB bitmap from bit valid_offset (as_key_input);
         build_flags: a uint8 device tensor, one byte per build row (or id), updated in place:
         the rows the probe's pairs would name are set to 1, nothing is cleared, so one
         tensor accumulates over batches. Not for a multi-GPU table (HJ_ERR_INVALID). No
-        host synchronisation: MatchResult.matched / .pairs read the statistics lazily."""
+        host synchronisation: MatchResult.matched / .pairs read the statistics lazily.
+        predicate: a columns.PairPredicate over the build side's columns and this batch's
+        (row i of a probe column belongs to keys[i]): only the pairs that pass it count
+        (hj_probe_match_filtered: a semi / anti join under a join filter; the walk over a
+        key's build rows stops at the first passing pair unless counts or flags are asked
+        for). bitmap=False (with a predicate only) asks for no bitmap: with build_flags as the
+        only output, candidates whose flag is already set are skipped."""
         if not (isinstance(keys, torch.Tensor) and keys.is_cuda):
             raise TypeError("probe_match takes a device tensor of keys")
         ki = as_key_input(keys, valid, valid_offset)
@@ -436,6 +476,8 @@ class HashTable:
                                             build_flags.is_contiguous()):
             raise TypeError("build_flags must be a contiguous uint8 device tensor")
         dev = keys.device
+        if predicate is not None:
+            return self._probe_match_filtered(ki, dev, counts, build_flags, predicate, bitmap)
         n = ki.n
         bitmap = torch.empty(((n + 63) // 64) * 8, dtype=torch.uint8, device=dev)
         cnt = torch.empty(n, dtype=torch.int32, device=dev) if counts else None

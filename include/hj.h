@@ -326,6 +326,54 @@ hj_status hj_probe_match(const hj_table* t, const void* keys, const uint8_t* val
                          uint32_t* out_counts, uint8_t* build_flags, int64_t nflags,
                          int64_t* d_stats, void* workspace, void* stream);
 
+/* Filtered match probe: the match probe under a join filter. Per probe row whether, and how
+ * often, some build row of its key also passes a pair predicate (the "pair filter" section
+ * below), without materialising pairs: a semi or anti join with a non-equi condition,
+ * EXISTS (... l2.k = l1.k AND l2.s <> l1.s). Replaces get_matching_indices followed by
+ * apply_join_filter_to_indices (src/shared/datafusion_private.rs:295-328) and then
+ * get_semi_indices / get_anti_indices / ConcurrentBitSet::set_ones
+ * (src/operator/probe_lookup_implementation/right_semi.rs:74-125, left_semi.rs:112-164);
+ * the filter applies before any marking, as in full.rs:140-175. The reference gathers the
+ * candidate rows of every pair and evaluates the filter on them; here the lookup, the walk
+ * over the key's build rows and the comparisons happen in registers. Opt-in: nothing else
+ * in the library calls it. Device pointers, asynchronous on `stream`, no allocation, no host
+ * synchronisation, no workspace; one launch.
+ *
+ * Let S be the pairs hj_probe_async would produce for the same table, keys, validity and n
+ * at unlimited capacity (probe_idx = row), and F the pairs of S that pass `pred` under the
+ * pair pass rule of the pair filter section, unchanged: both indices are checked against
+ * pred->build_rows / pred->probe_rows before any dereference, a term with a null operand
+ * is not true, the classes are INT / UINT / FLOAT (totalOrder) / BYTES. With explicit build
+ * ids the id is the pair's build_idx and also the row of the build columns: an id >=
+ * build_rows fails the pair and nothing is read. Row i of a probe column belongs to key i.
+ *   out_bitmap, out_counts, build_flags (each optional): exactly as hj_probe_match defines
+ *                them, with F in place of S. Bitmap words are written whole, bits at and
+ *                beyond n are 0, no pre-zeroing; null-key rows are 0. Counts are written for
+ *                every i < n. Flags are OR'ed into arbitrary prior contents, only ever
+ *                stored 1, ids >= nflags are skipped.
+ *   d_stats      (optional) device int64[3], overwritten: d_stats[0] = probe rows with a
+ *                pair in F if out_bitmap or out_counts is given, else -1; d_stats[1] = |F|
+ *                if out_counts is given, else -1; d_stats[2] = |S|, always (free from the
+ *                lookup: the candidate fan-out, for a planner).
+ * Cost. (a) With out_counts == NULL and no flags, a row's walk stops at its first passing
+ * pair. (b) With build_flags the only output requested, a candidate whose flag already
+ * reads 1 may be skipped (a plain racy byte load: flags are only ever stored 1). Otherwise
+ * every pair of S is evaluated once: there is no per-key claim as in hj_probe_match, since
+ * different probe rows of a key pass different build rows.
+ * Tables: every one-device table hj_probe_match accepts; a multi-GPU table returns
+ * HJ_ERR_INVALID. The call orders itself after the build and hj_table_free waits for it.
+ * n in [0, 2^32); n == 0 is valid and still writes d_stats. Errors, in this order:
+ * hj_pair_predicate_check's (so an invalid predicate is HJ_ERR_INVALID, with a message that
+ * names the term, on a machine without a GPU too); a null, unbuilt, failed or multi-GPU
+ * table, n out of range, null keys, bad nflags as hj_probe_match; a misaligned out_bitmap
+ * (8 bytes), out_counts (4) or d_stats (8); pred->probe_rows < n: HJ_ERR_INVALID. */
+struct hj_pair_predicate; /* defined in the pair filter section below */
+hj_status hj_probe_match_filtered(const hj_table* t, const void* keys, const uint8_t* validity,
+                                  int64_t validity_offset, int64_t n,
+                                  const struct hj_pair_predicate* pred, uint8_t* out_bitmap,
+                                  uint32_t* out_counts, uint8_t* build_flags, int64_t nflags,
+                                  int64_t* d_stats, void* stream);
+
 /* Pair plan and pair window: the pairs of one probe call in slices of bounded size.
  * Replaces get_matching_indices (src/shared/shared.rs:29-47); new: the reference emits a
  * probe batch's pairs in one piece, so its peak memory follows the join's fan-out. Here a
