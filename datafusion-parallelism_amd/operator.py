@@ -280,6 +280,9 @@ class GpuIndexLookup:
         composite key, then hj_filter_equal_pairs on the key columns."""
         arrays = ([probe_keys] if isinstance(probe_keys, (pa.Array, pa.ChunkedArray, DeviceColumn))
                   else list(probe_keys))
+        if self.build_is_empty:
+            return (torch.empty(0, dtype=torch.int64, device=self.device),
+                    torch.empty(0, dtype=torch.int32, device=self.device))
         if self._shared is not None and (self._shared.composite or not _is_simple_key(arrays)):
             return self._composite_matches(arrays, build_side_records)
         if not _is_simple_key(arrays):
@@ -293,6 +296,13 @@ class GpuIndexLookup:
         # the device validity bitmap goes to the probe as is, from bit voff (no host read)
         return self.table.probe(keys.key_tensor(), keys.valid, device_output=True, valid_offset=keys.voff,
                                 prefilter=self._prefilter())
+
+    @property
+    def build_is_empty(self) -> bool:
+        """No build row in any partition. The table's key type comes with the first non-empty
+        build batch; without one the table is an empty Int64 table whatever the join's key
+        is, so a probe does not ask it: there are no pairs."""
+        return self._shared is not None and self._shared.build_rows() == 0
 
     def _prefilter(self) -> "KeyFilter | None":
         return self._shared.key_filter() if self._shared is not None else None
@@ -326,7 +336,7 @@ class GpuIndexLookup:
             raise HjError(HJ_ERR_INVALID, "probe keys do not match the build keys (one Int32/Int64 column)")
         if composite and len(pcols) != len(sh.key_exprs):
             raise HjError(HJ_ERR_INVALID, f"{len(pcols)} probe key columns for {len(sh.key_exprs)} build key columns")
-        if pcols[0].length == 0:
+        if pcols[0].length == 0 or self.build_is_empty:
             return
         if composite:
             keys, valid = composite_keys(pcols)
@@ -392,6 +402,10 @@ class _SharedBuild:
             elif key_type != self.key_type:
                 raise HjError(HJ_ERR_INVALID, "all build batches must have the same key type")
             return self.table
+
+    def build_rows(self) -> int:
+        """Rows of all partitions' build batches (complete once the barrier is passed)."""
+        return sum(n for part in self.batches for _, n in part)
 
     def concatenated(self) -> DeviceRecordBatch:
         """Build RecordBatch in canonical order (partition 0 batches, then 1, ...): row i
@@ -600,6 +614,8 @@ def _takes_match_path(jt: JoinType, filter, lookup: GpuIndexLookup, key_cols: Se
     the match exact. More than 16 terms, or 16 columns of a side, keep the pair path."""
     sh = lookup._shared
     if not (sh is not None and sh.match_probe and jt in _MATCH_JOINS and n > 0 and lookup.table.devices is None):
+        return False
+    if lookup.build_is_empty:  # the pair path answers without the table
         return False
     if filter is not None and not isinstance(filter, CompareFilter):
         return False

@@ -8,6 +8,9 @@
   src/operator/probe_lookup_implementation/*.rs) - exact order for one partition and
   one probe batch, sorted multisets otherwise.
 * The gather / mark / select kernels against pyarrow.compute.take and numpy.
+* Further: output rows with payloads of every column type in test_gpu_join_rows.py (model:
+  join_rows_ref.py), the gathers' boundary sizes in test_gpu_gather_edges.py, the composite
+  key's promises in test_gpu_composite_keys.py.
 """
 import numpy as np
 import pyarrow as pa
