@@ -9,7 +9,7 @@ Importing the package does not need a GPU; calling into the kernels does, and fa
 loudly (``HJ_ERR_NO_DEVICE``) without one — there is no CPU fallback.
 """
 from ._lib import HjError, device_count, load  # noqa: F401
-from .table import HashTable, PairPlan  # noqa: F401
+from .table import FilteredPairPlan, HashTable, PairPlan  # noqa: F401
 from .key_filter import KeyFilter  # noqa: F401
 
-__all__ = ["HashTable", "HjError", "KeyFilter", "PairPlan", "device_count", "load"]
+__all__ = ["FilteredPairPlan", "HashTable", "HjError", "KeyFilter", "PairPlan", "device_count", "load"]

@@ -133,6 +133,9 @@ SIGNATURES = [
     ("hj_pair_plan_bytes", I64, [P, I64]),
     ("hj_pair_plan", I32, [P, P, P, I64, I64, P, P, P]),
     ("hj_pair_window", I32, [P, P, I64, P, U32, I64, I64, P, P, P, P]),
+    ("hj_pair_plan_filtered_bytes", I64, [P, I64]),
+    ("hj_pair_plan_filtered", I32, [P, P, P, I64, I64, ctypes.POINTER(HjPairPredicate), P, P, P, I64, P, P]),
+    ("hj_pair_window_filtered", I32, [P, P, I64, ctypes.POINTER(HjPairPredicate), P, U32, I64, I64, P, P, P, P]),
     ("hj_table_stream_wait", I32, [P, P]),
     ("hj_partition_workspace_bytes", I64, [I64, I32]),
     ("hj_radix_partition", I32, [I32, P, P, I64, P, U64, I64, I32, P, I32, I64, P, I32, P, P, P]),

@@ -2661,6 +2661,73 @@ hj_status hj_probe_match_filtered(const hj_table* t, const void* keys, const uin
     return note_probe(t, s);  // hj_table_free waits for it
 }
 
+// ---- filtered pair plan: the pair plan over the pairs that pass a pair predicate ----------
+
+int64_t hj_pair_plan_filtered_bytes(const hj_table* t, int64_t n) {
+    if (check_table(t) != HJ_OK) return -1;
+    if (t->multi) {
+        (void)fail(HJ_ERR_INVALID, kPlanMulti);
+        return -1;
+    }
+    if (check_probe_args(n, 0, 0, nullptr) != HJ_OK) return -1;
+    return pair_plan_filtered_layout(n).bytes;
+}
+
+hj_status hj_pair_plan_filtered(const hj_table* t, const void* keys, const uint8_t* validity, int64_t validity_offset,
+                                int64_t n, const hj_pair_predicate* pred, void* plan, uint8_t* out_bitmap,
+                                uint8_t* build_flags, int64_t nflags, int64_t* d_stats, void* stream) {
+    PairPred pr;
+    hj_status st = pair_pred(pred, &pr);  // first: an invalid predicate is HJ_ERR_INVALID without a GPU too
+    if (st != HJ_OK) return st;
+    if ((st = check_table(t)) != HJ_OK) return st;
+    if (t->multi) return fail(HJ_ERR_INVALID, kPlanMulti);
+    if ((st = check_probe_args(n, 0, 0, nullptr)) != HJ_OK) return st;
+    if (n > 0 && keys == nullptr) return fail(HJ_ERR_INVALID, "null keys");
+    if (nflags < 0 || (nflags > 0 && build_flags == nullptr)) return fail(HJ_ERR_INVALID, "bad build_flags / nflags");
+    if (plan == nullptr) return fail(HJ_ERR_INVALID, "null plan");
+    if ((reinterpret_cast<uintptr_t>(plan) & 7) || (reinterpret_cast<uintptr_t>(out_bitmap) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_stats) & 7))
+        return fail(HJ_ERR_INVALID, "plan, out_bitmap and d_stats must be 8-byte aligned");
+    if (pr.probe_rows < n)
+        return fail(HJ_ERR_INVALID, "hj_pair_plan_filtered: the predicate's probe_rows is below n (row i of the "
+                                    "probe columns belongs to key i)");
+    HIP_TRY(hipSetDevice(t->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((st = wait_built(t, s)) != HJ_OK) return st;  // the count orders itself after the build
+    HIP_TRY(launch_pair_plan_filtered(t->key_bytes, view_of(t), pr, keys, validity, validity_offset, n, plan,
+                                      out_bitmap, build_flags, nflags, d_stats, s));
+    return note_probe(t, s);  // hj_table_free waits for it
+}
+
+hj_status hj_pair_window_filtered(const hj_table* t, const void* plan, int64_t n, const hj_pair_predicate* pred,
+                                  const uint32_t* probe_ids, uint32_t probe_base, int64_t pair_lo, int64_t capacity,
+                                  uint64_t* out_build, uint32_t* out_probe, int64_t* d_written, void* stream) {
+    PairPred pr;
+    hj_status st = pair_pred(pred, &pr);
+    if (st != HJ_OK) return st;
+    if ((st = check_table(t)) != HJ_OK) return st;
+    if (t->multi) return fail(HJ_ERR_INVALID, kPlanMulti);
+    if (pair_lo < 0) return fail(HJ_ERR_INVALID, "negative pair_lo");
+    if ((st = check_probe_args(n, probe_base, capacity, nullptr)) != HJ_OK) return st;
+    if (capacity > ((int64_t)1 << 42)) return fail(HJ_ERR_INVALID, "capacity exceeds 2^42 pairs");
+    if (probe_ids != nullptr && probe_base != 0)
+        return fail(HJ_ERR_INVALID, "probe_ids and probe_base are exclusive: add the base to the ids");
+    if (plan == nullptr) return fail(HJ_ERR_INVALID, "null plan");
+    if ((reinterpret_cast<uintptr_t>(plan) & 7) || (reinterpret_cast<uintptr_t>(d_written) & 7) ||
+        (reinterpret_cast<uintptr_t>(out_build) & 7) || (reinterpret_cast<uintptr_t>(out_probe) & 3))
+        return fail(HJ_ERR_INVALID, "plan, d_written and out_build must be 8-byte, out_probe 4-byte aligned");
+    if (capacity > 0 && (out_build == nullptr || out_probe == nullptr))
+        return fail(HJ_ERR_INVALID, "null output with capacity > 0");
+    if (pr.probe_rows < n)
+        return fail(HJ_ERR_INVALID, "hj_pair_window_filtered: the predicate's probe_rows is below n (the plan's)");
+    HIP_TRY(hipSetDevice(t->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((st = wait_built(t, s)) != HJ_OK) return st;  // the window reads the table again
+    HIP_TRY(launch_pair_window_filtered(view_of(t), pr, plan, n, probe_ids, probe_base, pair_lo, capacity, out_build,
+                                        out_probe, d_written, s));
+    return note_probe(t, s);
+}
+
 hj_status hj_gen_perm_keys(int64_t* out, int64_t n, int64_t mul, int64_t range, void* stream) {
     if (device_count() == 0) return fail(HJ_ERR_NO_DEVICE, "no GPU visible");
     if (range <= 0 || n < 0) return fail(HJ_ERR_INVALID, "bad range");

@@ -5418,6 +5418,394 @@ hipError_t launch_probe_match_filtered(int key_bytes, const TableView& tv, const
 }
 
 // ---------------------------------------------------------------------------
+// filtered pair plan: the pair plan under a pair predicate, whose windows hold F, the pairs
+// of the probe that pass it, not S. What lookup_inner_join_probe_batch (inner.rs:79-129)
+// keeps of get_matching_indices (src/shared/shared.rs:29-47) once
+// apply_join_filter_to_indices (src/shared/datafusion_private.rs:295-328) has dropped the
+// failing pairs - the filter before any marking, as in full.rs:140-175 - without S ever
+// reaching memory. Count -> scan -> write, every pass a launch of its own: no workgroup
+// waits for another.
+//
+//   count  pair_plan_filtered_count_kernel  probe_match_filtered_kernel's full walk (no
+//          first-pass exit, no flag skip: the counts are exact). Keeps every row's ref and
+//          F-count and, per block of kPlanBlockRows rows, (rows with a pair in F, its pairs
+//          in F); bitmap and flags as the filtered match probe writes them; |S| by one
+//          atomic per workgroup into the plan's header.
+//   scan   pair_plan_filtered_scan_kernel   one workgroup: exclusive scan of the block
+//          totals in place, the grand totals behind the last block, the header and d_stats.
+//   emit   pair_window_filtered_kernel      the same grid of blocks. A block whose scanned
+//          range misses the window leaves after two loads. Otherwise its rows' F-counts
+//          are scanned (64-bit ranks) and every row whose passing pairs meet the window
+//          walks its candidates again, in the count's order: pair k of the row goes to rank
+//          offset + k. Rows without a pair in F are never walked again.
+// ---------------------------------------------------------------------------
+FilteredPlanLayout pair_plan_filtered_layout(int64_t n) {
+    FilteredPlanLayout L;
+    L.nblocks = (n + kPlanBlockRows - 1) / kPlanBlockRows;
+    L.refs = kPlanHeaderBytes;
+    L.counts = L.refs + ((4 * n + 15) & ~(int64_t)15);
+    L.blocks = L.counts + ((4 * n + 15) & ~(int64_t)15);
+    L.bytes = L.blocks + 16 * (L.nblocks + 1);
+    return L;
+}
+
+template <typename K, bool HAS_VALID, bool BYTES>
+__global__ void __launch_bounds__(kMatchThreads)
+pair_plan_filtered_count_kernel(TableView tv, PairPred pr, const void* __restrict__ keys,
+                                const uint8_t* __restrict__ valid, int64_t voff, int64_t n, bool vec,
+                                unsigned long long* __restrict__ out_bitmap, uint8_t* flags, uint64_t nflags,
+                                uint32_t* __restrict__ refs, uint32_t* __restrict__ counts, bool svec,
+                                unsigned long long* __restrict__ btot, unsigned long long* __restrict__ cand_total) {
+    __shared__ unsigned long long s_m[kMatchThreads / 64], s_p[kMatchThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t nwords = (n + 63) >> 6;
+    unsigned long long cand = 0;
+    for (int64_t blk = blockIdx.x; blk * kMatchRows < n; blk += gridDim.x) {
+        const int64_t wrow0 = blk * kMatchRows + (int64_t)wave * 256;
+        const int64_t row0 = wrow0 + (int64_t)lane * 4;
+        unsigned long long matched = 0, pairs = 0;
+        if (wrow0 < n) {  // the whole wave (a wave past n only joins the block's totals)
+            uint32_t ref[4] = {kMiss, kMiss, kMiss, kMiss}, cnt[4] = {0, 0, 0, 0};
+            if (row0 < n) lookup4<K, HAS_VALID>(tv, keys, valid, voff, n, vec, row0, ref, cnt);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                cnt[q] = resolve_count(tv.dup_rows, ref[q], cnt[q], tv.off_mask);
+                cand += cnt[q];
+            }
+            uint32_t hit[4] = {0, 0, 0, 0};  // hit[q]: the row's pairs in F
+#pragma unroll 1
+            for (int q = 0; q < 4; ++q) {  // keys the owning lane walks
+                const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q);
+                uint32_t h = 0;
+                if (c != 0 && c <= kMatchLaneWalk) {  // a matched row: row0 + q < n
+                    const uint32_t prow = (uint32_t)(row0 + q);
+                    for (uint32_t j = 0; j < c; ++j) {
+                        const uint32_t row = (r & kDupFlag) ? dup_ref_row(tv.dup_rows, r, tv.off_mask, j) : r;
+                        h += mf_candidate<BYTES, kMfFull>(tv, pr, row, prow, flags, nflags, false);
+                    }
+                }
+                mf_put4(hit, q, h);
+            }
+#pragma unroll 1
+            for (int q = 0; q < 4; ++q) {  // larger keys: the wave walks them one after another
+                const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q);
+                uint32_t h = mf_sel4(hit, q);
+                unsigned long long m = __ballot(c > kMatchLaneWalk);
+                while (m) {
+                    const int src = __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    const uint32_t sr = __shfl(r, src, 64), sc = __shfl(c, src, 64);
+                    const uint32_t prow = (uint32_t)(wrow0 + (int64_t)src * 4 + q);
+                    uint32_t tot = 0;
+                    for (uint32_t j0 = 0; j0 < sc; j0 += 64) {  // sc <= the build's rows < 2^32 - 64
+                        const uint32_t j = j0 + (uint32_t)lane;
+                        bool pass = false;
+                        if (j < sc)
+                            pass = mf_candidate<BYTES, kMfFull>(tv, pr, dup_ref_row(tv.dup_rows, sr, tv.off_mask, j),
+                                                                prow, flags, nflags, false);
+                        tot += (uint32_t)__popcll(__ballot(pass));
+                    }
+                    if (lane == src) h = tot;
+                }
+                mf_put4(hit, q, h);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                matched += hit[q] != 0;
+                pairs += hit[q];
+            }
+            if (out_bitmap != nullptr) {
+                unsigned long long b[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) b[q] = __ballot(hit[q] != 0);
+                if (lane < 4) {  // lane w assembles word w of the wave's four
+                    unsigned long long word = 0;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) word |= spread16_by4(b[q] >> (16 * lane)) << q;
+                    const int64_t widx = (wrow0 >> 6) + lane;
+                    if (widx < nwords) out_bitmap[widx] = word;  // rows >= n have no candidate: tail bits 0
+                }
+            }
+            if (svec && row0 + 4 <= n) {
+                *reinterpret_cast<uint4*>(refs + row0) = make_uint4(ref[0], ref[1], ref[2], ref[3]);
+                *reinterpret_cast<uint4*>(counts + row0) = make_uint4(hit[0], hit[1], hit[2], hit[3]);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (row0 + q < n) {
+                        refs[row0 + q] = ref[q];
+                        counts[row0 + q] = hit[q];
+                    }
+            }
+        }
+        const unsigned long long wm = wave_sum<unsigned long long>(matched);
+        const unsigned long long wp = wave_sum<unsigned long long>(pairs);
+        if (lane == 0) { s_m[wave] = wm; s_p[wave] = wp; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long tm = 0, tp = 0;
+            for (int w = 0; w < kMatchThreads / 64; ++w) { tm += s_m[w]; tp += s_p[w]; }
+            btot[2 * blk] = tm;
+            btot[2 * blk + 1] = tp;
+        }
+        __syncthreads();
+    }
+    // |S|: wave reduction, then one atomic per workgroup
+    const unsigned long long wc = wave_sum<unsigned long long>(cand);
+    if (lane == 0) s_m[wave] = wc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tc = 0;
+        for (int w = 0; w < kMatchThreads / 64; ++w) tc += s_m[w];
+        if (tc) atomicAdd(cand_total, tc);
+    }
+}
+
+constexpr int kFpScanThreads = 1024;
+constexpr int kFpScanPer = 8;  // block totals per thread and round
+
+// header: [0] rows with a pair in F, [1] |F|, [2] |S| (zeroed before the count, which adds to
+// it); btot[2 * nblocks], btot[2 * nblocks + 1]: the same totals, so that block b's range of
+// ranks is [btot[2b + 1], btot[2b + 3]) for every b
+__global__ void __launch_bounds__(kFpScanThreads)
+pair_plan_filtered_scan_kernel(unsigned long long* __restrict__ btot, int64_t nblocks,
+                               unsigned long long* __restrict__ header, long long* __restrict__ d_stats) {
+    __shared__ unsigned long long s_w[kFpScanThreads / 64];
+    unsigned long long run_m = 0, run_p = 0;
+    for (int64_t base = 0; base < nblocks; base += (int64_t)kFpScanThreads * kFpScanPer) {
+        const int64_t i0 = base + (int64_t)threadIdx.x * kFpScanPer;
+        unsigned long long vm[kFpScanPer], vp[kFpScanPer], sm = 0, sp = 0;
+#pragma unroll
+        for (int q = 0; q < kFpScanPer; ++q) {
+            const bool in = i0 + q < nblocks;
+            vm[q] = in ? btot[2 * (i0 + q)] : 0ull;
+            vp[q] = in ? btot[2 * (i0 + q) + 1] : 0ull;
+            sm += vm[q];
+            sp += vp[q];
+        }
+        unsigned long long tm, tp;
+        unsigned long long em = run_m + block_excl_scan<unsigned long long>(sm, s_w, &tm);
+        unsigned long long ep = run_p + block_excl_scan<unsigned long long>(sp, s_w, &tp);
+#pragma unroll
+        for (int q = 0; q < kFpScanPer; ++q) {
+            if (i0 + q < nblocks) {
+                btot[2 * (i0 + q)] = em;
+                btot[2 * (i0 + q) + 1] = ep;
+            }
+            em += vm[q];
+            ep += vp[q];
+        }
+        run_m += tm;
+        run_p += tp;
+    }
+    if (threadIdx.x == 0) {
+        btot[2 * nblocks] = run_m;
+        btot[2 * nblocks + 1] = run_p;
+        header[0] = run_m;
+        header[1] = run_p;
+        if (d_stats != nullptr) {
+            d_stats[0] = (long long)run_m;
+            d_stats[1] = (long long)run_p;
+            d_stats[2] = (long long)header[2];
+        }
+    }
+}
+
+hipError_t launch_pair_plan_filtered(int key_bytes, const TableView& tv, const PairPred& pr, const void* keys,
+                                     const uint8_t* valid, int64_t voff, int64_t n, void* plan, uint8_t* out_bitmap,
+                                     uint8_t* flags, int64_t nflags, int64_t* d_stats, hipStream_t s) {
+    const FilteredPlanLayout L = pair_plan_filtered_layout(n);
+    char* p = static_cast<char*>(plan);
+    unsigned long long* header = reinterpret_cast<unsigned long long*>(p);
+    uint32_t* refs = reinterpret_cast<uint32_t*>(p + L.refs);
+    uint32_t* counts = reinterpret_cast<uint32_t*>(p + L.counts);
+    unsigned long long* btot = reinterpret_cast<unsigned long long*>(p + L.blocks);
+    hipError_t e = hipMemsetAsync(header, 0, kPlanHeaderBytes, s);
+    if (e != hipSuccess) return e;
+    if (n > 0) {
+        const bool mark = flags != nullptr && nflags > 0;
+        bool bytes = false;  // the BYTES compare loop only where a term needs it
+        for (int t = 0; t < pr.nterms; ++t) bytes = bytes || pr.t[t].cls == kPfBytes;
+        const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15) == 0;
+        const bool svec = (reinterpret_cast<uintptr_t>(plan) & 15) == 0;
+        const unsigned grid = (unsigned)std::min<int64_t>(L.nblocks, kMatchMaxBlocks);
+        unsigned long long* bm = reinterpret_cast<unsigned long long*>(out_bitmap);
+#define DFP_FPC(KT, HV, BY)                                                                                          \
+    pair_plan_filtered_count_kernel<KT, HV, BY><<<grid, kMatchThreads, 0, s>>>(                                      \
+        tv, pr, keys, valid, voff, n, vec, bm, mark ? flags : nullptr, mark ? (uint64_t)nflags : 0, refs, counts, svec, \
+        btot, header + 2)
+#define DFP_FPC_K(KT, HV)                        \
+    do {                                         \
+        if (bytes) DFP_FPC(KT, HV, true);        \
+        else DFP_FPC(KT, HV, false);             \
+    } while (0)
+        if (key_bytes == 8) {
+            if (valid) DFP_FPC_K(int64_t, true); else DFP_FPC_K(int64_t, false);
+        } else {
+            if (valid) DFP_FPC_K(int32_t, true); else DFP_FPC_K(int32_t, false);
+        }
+#undef DFP_FPC_K
+#undef DFP_FPC
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    pair_plan_filtered_scan_kernel<<<1, kFpScanThreads, 0, s>>>(btot, L.nblocks, header,
+                                                                reinterpret_cast<long long*>(d_stats));
+    return hipGetLastError();
+}
+
+// Inclusive wave64 scan of a u64 < 2^40 in two DPP scans: the low 24 bits (64 lanes: < 2^30)
+// and the bits above them (< 2^16 each: < 2^22). A lane's four F-counts are below 2^34.
+__device__ __forceinline__ unsigned long long wave_incl_scan40_dpp(unsigned long long v) {
+    const uint32_t lo = wave_incl_scan_dpp((uint32_t)v & 0xFFFFFFu);
+    const uint32_t hi = wave_incl_scan_dpp((uint32_t)(v >> 24));
+    return ((unsigned long long)hi << 24) + lo;
+}
+
+template <bool BYTES, bool HAS_PROBE_IDS>
+__global__ void __launch_bounds__(kMatchThreads)
+pair_window_filtered_kernel(TableView tv, PairPred pr, const uint32_t* __restrict__ refs,
+                            const uint32_t* __restrict__ counts, bool svec, int64_t n, int64_t nblocks,
+                            const unsigned long long* __restrict__ btot, const uint32_t* __restrict__ probe_ids,
+                            uint32_t pbase, unsigned long long pair_lo, unsigned long long cap,
+                            uint64_t* __restrict__ out_b, uint32_t* __restrict__ out_p,
+                            long long* __restrict__ d_written) {
+    __shared__ unsigned long long s_w[kMatchThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && d_written != nullptr) {
+        const unsigned long long total = btot[2 * nblocks + 1];
+        const unsigned long long w = pair_lo < total ? total - pair_lo : 0ull;
+        *d_written = (long long)(w < cap ? w : cap);
+    }
+    if ((int64_t)blockIdx.x >= nblocks || cap == 0) return;
+    // the block's ranks [base, next) against the window [pair_lo, hi); every rank is below
+    // |F|, so the window's end needs no clamp (pair_lo < 2^63, cap <= 2^42: no overflow)
+    const unsigned long long base = btot[2 * (int64_t)blockIdx.x + 1], next = btot[2 * (int64_t)blockIdx.x + 3];
+    const unsigned long long hi = pair_lo + cap;
+    if (next <= pair_lo || base >= hi) return;  // the whole workgroup
+    const int64_t wrow0 = (int64_t)blockIdx.x * kPlanBlockRows + (int64_t)wave * 256;
+    const int64_t row0 = wrow0 + (int64_t)lane * 4;
+    uint32_t ref[4] = {kMiss, kMiss, kMiss, kMiss}, fc[4] = {0, 0, 0, 0};
+    if (svec && row0 + 4 <= n) {
+        const uint4 r = *reinterpret_cast<const uint4*>(refs + row0);
+        const uint4 c = *reinterpret_cast<const uint4*>(counts + row0);
+        ref[0] = r.x; ref[1] = r.y; ref[2] = r.z; ref[3] = r.w;
+        fc[0] = c.x; fc[1] = c.y; fc[2] = c.z; fc[3] = c.w;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (row0 + q < n) {
+                ref[q] = refs[row0 + q];
+                fc[q] = counts[row0 + q];
+            }
+    }
+    // 64-bit exclusive prefix of the F-counts inside the block
+    const unsigned long long mine = (unsigned long long)fc[0] + fc[1] + fc[2] + fc[3];
+    const unsigned long long incl = wave_incl_scan40_dpp(mine);
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    unsigned long long off = base + (incl - mine);
+    for (int w = 0; w < wave; ++w) off += s_w[w];
+    // off4[q]: rank of the row's first passing pair; cnt[q]: its candidates if any of its
+    // passing pairs is in the window, else 0 (the row is not walked).
+    // The candidate count is not kept in the plan: ref_count(ref) here must equal the count
+    // pass's resolve_count(lookup4's count), because the lane / wave split below and the walk's
+    // order follow it. It does for every layout - a single row 1, a packed or run count from the
+    // ref's bits, else dup_rows[offset], which is also what lookup4's inline bucket count and
+    // the side bucket's row count of key 0 stand for. A layout whose lookup count is not
+    // recoverable from the ref has to store the count in the plan (as pair_plan_lookup_kernel does).
+    unsigned long long off4[4];
+    uint32_t cnt[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        off4[q] = off;
+        off += fc[q];
+        const bool in = fc[q] != 0 && off > pair_lo && off4[q] < hi;
+        cnt[q] = in ? ref_count(tv.dup_rows, ref[q], tv.off_mask) : 0u;
+    }
+#pragma unroll 1
+    for (int q = 0; q < 4; ++q) {  // keys the owning lane walks: adjacent lanes' rows are adjacent ranks
+        const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q), f = mf_sel4(fc, q);
+        if (c != 0 && c <= kMatchLaneWalk) {
+            const unsigned long long o = q == 0 ? off4[0] : (q == 1 ? off4[1] : (q == 2 ? off4[2] : off4[3]));
+            const uint32_t prow = (uint32_t)(row0 + q);
+            const uint32_t pid = HAS_PROBE_IDS ? probe_ids[prow] : prow + pbase;
+            uint32_t k = 0;
+            for (uint32_t j = 0; j < c && k < f && o + k < hi; ++j) {
+                const uint32_t row = (r & kDupFlag) ? dup_ref_row(tv.dup_rows, r, tv.off_mask, j) : r;
+                const uint64_t id = tv.row_ids != nullptr ? tv.row_ids[row] : (uint64_t)row;
+                if (pf_pair_passes<BYTES>(pr, true, id, prow)) {
+                    const unsigned long long rank = o + k;
+                    if (rank >= pair_lo) {  // rank < hi: the loop's condition
+                        out_b[rank - pair_lo] = id;
+                        out_p[rank - pair_lo] = pid;
+                    }
+                    ++k;
+                }
+            }
+        }
+    }
+#pragma unroll 1
+    for (int q = 0; q < 4; ++q) {  // larger keys: the wave walks them, a round's stores are contiguous
+        const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q), f = mf_sel4(fc, q);
+        const unsigned long long o = q == 0 ? off4[0] : (q == 1 ? off4[1] : (q == 2 ? off4[2] : off4[3]));
+        unsigned long long m = __ballot(c > kMatchLaneWalk);
+        while (m) {
+            const int src = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const uint32_t sr = __shfl(r, src, 64), sc = __shfl(c, src, 64), sf = __shfl(f, src, 64);
+            const unsigned long long so = __shfl(o, src, 64);
+            const uint32_t prow = (uint32_t)(wrow0 + (int64_t)src * 4 + q);
+            const uint32_t pid = HAS_PROBE_IDS ? probe_ids[prow] : prow + pbase;
+            uint32_t tot = 0;  // the row's passing pairs before this round
+            for (uint32_t j0 = 0; j0 < sc && tot < sf && so + tot < hi; j0 += 64) {  // wave-uniform
+                const uint32_t j = j0 + (uint32_t)lane;
+                bool pass = false;
+                uint64_t id = 0;
+                if (j < sc) {
+                    const uint32_t row = dup_ref_row(tv.dup_rows, sr, tv.off_mask, j);
+                    id = tv.row_ids != nullptr ? tv.row_ids[row] : (uint64_t)row;
+                    pass = pf_pair_passes<BYTES>(pr, true, id, prow);
+                }
+                const unsigned long long b = __ballot(pass);
+                const uint32_t k = tot + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+                const unsigned long long rank = so + k;
+                if (pass && k < sf && rank >= pair_lo && rank < hi) {
+                    out_b[rank - pair_lo] = id;
+                    out_p[rank - pair_lo] = pid;
+                }
+                tot += (uint32_t)__popcll(b);
+            }
+        }
+    }
+}
+
+hipError_t launch_pair_window_filtered(const TableView& tv, const PairPred& pr, const void* plan, int64_t n,
+                                       const uint32_t* probe_ids, uint32_t probe_base, int64_t pair_lo,
+                                       int64_t capacity, uint64_t* out_b, uint32_t* out_p, int64_t* d_written,
+                                       hipStream_t s) {
+    const FilteredPlanLayout L = pair_plan_filtered_layout(n);
+    const char* p = static_cast<const char*>(plan);
+    const uint32_t* refs = reinterpret_cast<const uint32_t*>(p + L.refs);
+    const uint32_t* counts = reinterpret_cast<const uint32_t*>(p + L.counts);
+    const unsigned long long* btot = reinterpret_cast<const unsigned long long*>(p + L.blocks);
+    bool bytes = false;
+    for (int t = 0; t < pr.nterms; ++t) bytes = bytes || pr.t[t].cls == kPfBytes;
+    const bool svec = (reinterpret_cast<uintptr_t>(plan) & 15) == 0;
+    const unsigned grid = (unsigned)std::max<int64_t>(L.nblocks, 1);  // block 0 writes *d_written
+#define DFP_FPW(BY, PI)                                                                                         \
+    pair_window_filtered_kernel<BY, PI><<<grid, kMatchThreads, 0, s>>>(                                         \
+        tv, pr, refs, counts, svec, n, L.nblocks, btot, probe_ids, probe_base, (unsigned long long)pair_lo,      \
+        (unsigned long long)capacity, out_b, out_p, reinterpret_cast<long long*>(d_written))
+    if (bytes) {
+        if (probe_ids != nullptr) DFP_FPW(true, true); else DFP_FPW(true, false);
+    } else {
+        if (probe_ids != nullptr) DFP_FPW(false, true); else DFP_FPW(false, false);
+    }
+#undef DFP_FPW
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // pair plan, pass 1: the match probe's lookup, kept per row. Every row's ref and resolved
 // pair count go to the plan's scratch, and every block of kPlanBlockRows rows leaves its
 // (matched rows, pairs) totals; the scan of those totals and the compaction are launches

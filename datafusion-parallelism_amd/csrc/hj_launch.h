@@ -308,6 +308,33 @@ hipError_t launch_probe_match_filtered(int key_bytes, const TableView& tv, const
                                        uint32_t* out_counts, uint8_t* flags, int64_t nflags, int64_t* d_stats,
                                        hipStream_t s);
 
+// ---- filtered pair plan (hj_kernels.hip: count, scan and emit under a pair predicate) ----
+// The plan of a probe call's n rows under `pr`, in caller memory of
+// pair_plan_filtered_layout(n).bytes bytes (8-byte aligned):
+//   header   u64 rows with a pair in F, u64 |F|, u64 |S| (kPlanHeaderBytes reserved)
+//   refs     u32[n]: every row's ref, from the lookup
+//   counts   u32[n]: every row's pairs in F
+//   blocks   u64[2 * (blocks + 1)]: per block of kPlanBlockRows rows the exclusive scan of
+//            (rows with a pair in F, pairs in F); the last entry holds the totals
+struct FilteredPlanLayout {
+    int64_t refs, counts, blocks, bytes;  // byte offsets of the sections; total size
+    int64_t nblocks;
+};
+FilteredPlanLayout pair_plan_filtered_layout(int64_t n);
+// count + scan (a memset of the header before them): out_bitmap / flags as
+// launch_probe_match_filtered defines them (each optional); d_stats (optional) int64[3] =
+// rows with a pair in F, |F|, |S|. n >= 0. The caller has ordered `s` after the build and
+// checked pr.probe_rows >= n.
+hipError_t launch_pair_plan_filtered(int key_bytes, const TableView& tv, const PairPred& pr, const void* keys,
+                                     const uint8_t* valid, int64_t voff, int64_t n, void* plan, uint8_t* out_bitmap,
+                                     uint8_t* flags, int64_t nflags, int64_t* d_stats, hipStream_t s);
+// pairs [pair_lo, pair_lo + capacity) of F in canonical order -> out_b / out_p from index 0;
+// *d_written (optional) = pairs written. One workgroup per block of kPlanBlockRows rows.
+hipError_t launch_pair_window_filtered(const TableView& tv, const PairPred& pr, const void* plan, int64_t n,
+                                       const uint32_t* probe_ids, uint32_t probe_base, int64_t pair_lo,
+                                       int64_t capacity, uint64_t* out_b, uint32_t* out_p, int64_t* d_written,
+                                       hipStream_t s);
+
 // ---- generators ----------------------------------------------------------
 hipError_t launch_gen_perm(int64_t* out, int64_t n, int64_t mul, int64_t range, hipStream_t s);
 hipError_t launch_gen_uniform(int64_t* out, int64_t n, uint64_t seed, int64_t range,

@@ -368,8 +368,10 @@ class _SharedBuild:
     """State shared by all partitions of one build (JoinStateInstances)."""
 
     def __init__(self, parallelism: int, device: int, devices: Sequence[int] | None = None, plan: str = "auto",
-                 prefilter: bool = False, match_probe: bool = False, max_output_rows: int | None = None):
+                 prefilter: bool = False, match_probe: bool = False, max_output_rows: int | None = None,
+                 filtered_probe: bool = False):
         self.parallelism = parallelism
+        self.filtered_probe = filtered_probe  # pair joins under a device predicate emit only passing pairs
         self.max_output_rows = max_output_rows  # probe batches emit in windows of at most this many rows
         self.prefilter = prefilter      # probes go through a key filter over the build keys
         self.match_probe = match_probe  # semi / anti joins probe for matches, not pairs (probe_batch)
@@ -466,7 +468,7 @@ class BuildImplementation:
     def __init__(self, build_implementation_version: JoinReplacement, parallelism: int,
                  input_schema: pa.Schema | None = None, device: int = 0, devices: Sequence[int] | None = None,
                  plan: str = "auto", prefilter: bool = False, match_probe: bool = False,
-                 max_output_rows: int | None = None):
+                 max_output_rows: int | None = None, filtered_probe: bool = False):
         """max_output_rows: None (default) changes nothing. An integer N >= 1 bounds the memory
         of every probe batch by N instead of by the join's fan-out: the batch's pairs are
         planned once (HashTable.pair_plan) and taken window by window, each of at most N
@@ -499,6 +501,25 @@ class BuildImplementation:
         0.89 ms, LeftSemi 1.61 against 1.55 ms). It wins where keys repeat: a
         key of c build rows hit by m probe rows costs m + c, not m * c (1000 rows per key:
         0.08 ms against 22.9 ms), and it runs joins whose pairs no buffer holds.
+        filtered_probe: Inner, Left, Right and Full probe batches under a CompareFilter - or
+        on a composite key without a filter, whose candidates then only have to pass the key
+        equalities - write only the pairs that pass (HashTable.pair_plan(predicate=...),
+        hj_pair_plan_filtered): a count walk evaluates every candidate in registers and also
+        leaves the visited build rows (Left / Full) and the matched-probe bitmap (Right /
+        Full), a second walk writes the passing pairs at scanned offsets. The candidate pairs
+        of the equi-join, hj_filter_equal_pairs and the select never touch memory. The same
+        conditions as match_probe's: the table on one device, a non-empty build side, one
+        Int32/Int64 key column or a composite key of exact `==` columns within 16 terms and
+        columns. With max_output_rows=N every emitted batch then has up to N *passing* pairs
+        and no window is empty. The remaining cases silently take the pair path: a callable
+        JoinFilter, `devices=`, float / decimal / 16-byte key columns, more than 16 terms or
+        columns, and semi / anti joins (match_probe's). Output rows and their order are the
+        same. This path does not use the key filter: with prefilter=True too, the filter
+        serves only the probes that take the pair path. Off by default: every candidate is
+        evaluated twice. Measured: on 10^9 candidates of which 9.5 % pass,
+        1.16 GB of buffers instead of 24 GB at 5 % more time; 1.31 x faster where nearly all
+        pass; 0.40 x on a join of one pair per match; and 0.13 x with max_output_rows = 2^20
+        over keys of 1000 rows, where a window keeps only a few workgroups busy.
         devices: build one table over these GPUs of the node (hj_build_begin_multi;
         DataFusion runs every partition in one process, so the in-process multi-GPU table
         is the drop-in's node-wide form); plan "auto" | "broadcast" | "radix" (the build
@@ -517,7 +538,8 @@ class BuildImplementation:
                 raise HjError(HJ_ERR_INVALID, "max_output_rows is not available on a multi-GPU table (devices=): "
                                               "the pair plan is defined for one-device tables")
         self.parallelism = parallelism
-        self._shared = _SharedBuild(parallelism, device, devices, plan, prefilter, match_probe, max_output_rows)
+        self._shared = _SharedBuild(parallelism, device, devices, plan, prefilter, match_probe, max_output_rows,
+                                    bool(filtered_probe))
         self._shared.schema = input_schema
 
     def build_side(self, partition: int, stream: Iterable[pa.RecordBatch], build_expressions: Sequence[str | int],
@@ -617,6 +639,14 @@ def _takes_match_path(jt: JoinType, filter, lookup: GpuIndexLookup, key_cols: Se
         return False
     if lookup.build_is_empty:  # the pair path answers without the table
         return False
+    return _device_predicate_ok(filter, lookup, key_cols, build_side_records)
+
+
+def _device_predicate_ok(filter, lookup: GpuIndexLookup, key_cols: Sequence[DeviceColumn], build_side_records) -> bool:
+    """The rule _takes_match_path states for the filter and the key (shared with the filtered
+    pair plan): no filter or a CompareFilter; one Int32/Int64 key column, or a composite key
+    of exact `==` columns whose terms and columns stay within 16 with the filter's."""
+    sh = lookup._shared
     if filter is not None and not isinstance(filter, CompareFilter):
         return False
     if _simple_match_key(lookup, key_cols):
@@ -633,6 +663,70 @@ def _takes_match_path(jt: JoinType, filter, lookup: GpuIndexLookup, key_cols: Se
     return nt + nk <= 16 and nl + nk <= 16 and nr + nk <= 16
 
 
+def _probe_keys_and_predicate(filter: "CompareFilter | None", build_side_records, lookup: GpuIndexLookup,
+                              probe_batch: pa.RecordBatch, probe_cols: list[DeviceColumn],
+                              key_cols: list[DeviceColumn]):
+    """(keys, valid, valid_offset, predicate) of one probe batch for the table's predicate
+    calls (_device_predicate_ok holds): the key tensor of one Int32/Int64 column or the
+    composite hashes, and the predicate _apply_filter would build plus one `==` term per
+    column of a composite key. predicate is None without a filter on one Int32/Int64 key."""
+    n = probe_batch.num_rows
+    simple = _simple_match_key(lookup, key_cols)
+    if simple:
+        k = key_cols[0]
+        keys, valid, voff = k.key_tensor(), k.valid, k.voff
+    else:
+        (keys, valid), voff = composite_keys(key_cols), 0
+    if simple and filter is None:
+        return keys, valid, voff, None
+    build_cols = lookup.build_columns(build_side_records)
+    bnames, nb = list(build_side_records.schema.names), build_side_records.num_rows
+    eq = []
+    if not simple:
+        sh = lookup._shared
+        eq = [(build_cols[e if isinstance(e, int) else build_side_records.schema.get_field_index(e)], k)
+              for e, k in zip(sh.key_exprs, key_cols)]
+    if filter is not None:
+        pred = filter.predicate(build_cols, bnames, probe_cols, list(probe_batch.schema.names), nb, n, eq_keys=eq)
+    else:
+        pred = PairPredicate([b for b, _ in eq], [p for _, p in eq],
+                             [(("build", i), "==", ("probe", i)) for i in range(len(eq))], nb, n)
+    return keys, valid, voff, pred
+
+
+_PAIR_JOINS = (JoinType.Inner, JoinType.Left, JoinType.Right, JoinType.Full)
+
+
+def _takes_filtered_path(jt: JoinType, filter, lookup: GpuIndexLookup, key_cols: Sequence[DeviceColumn], n: int,
+                         build_side_records=None) -> bool:
+    """BuildImplementation(filtered_probe=True): an Inner, Left, Right or Full join on a
+    one-device table under a CompareFilter - or on a composite key without a filter, whose
+    predicate is the key equalities alone - with a key _device_predicate_ok accepts. Then only
+    the pairs that pass reach memory (HashTable.pair_plan(predicate=...)). Everything else
+    keeps the pair path."""
+    sh = lookup._shared
+    if not (sh is not None and sh.filtered_probe and jt in _PAIR_JOINS and n > 0 and lookup.table.devices is None):
+        return False
+    if lookup.build_is_empty:
+        return False
+    if not _device_predicate_ok(filter, lookup, key_cols, build_side_records):
+        return False
+    return filter is not None or not _simple_match_key(lookup, key_cols)
+
+
+def _filtered_plan(jt: JoinType, filter: "CompareFilter | None", build_side_records, lookup: GpuIndexLookup,
+                   probe_batch: pa.RecordBatch, probe_cols: list[DeviceColumn], key_cols: list[DeviceColumn],
+                   build_visited: torch.Tensor | None):
+    """The filtered pair plan of one probe batch (_takes_filtered_path holds). The one count
+    walk also leaves the outer joins' bookkeeping: the visited build rows of Left / Full
+    (set_ones) and the matched-probe bitmap of Right / Full, so no mark_rows over pairs."""
+    keys, valid, voff, pred = _probe_keys_and_predicate(filter, build_side_records, lookup, probe_batch, probe_cols,
+                                                        key_cols)
+    flags = build_visited if jt in (JoinType.Left, JoinType.Full) else None
+    return lookup.table.pair_plan(keys, valid, valid_offset=voff, predicate=pred, build_flags=flags,
+                                  bitmap=jt in (JoinType.Right, JoinType.Full))
+
+
 def _match_probe(jt: JoinType, filter: "CompareFilter | None", build_side_records, lookup: GpuIndexLookup,
                  probe_batch: pa.RecordBatch, probe_cols: list[DeviceColumn], key_cols: list[DeviceColumn],
                  build_visited: torch.Tensor | None) -> torch.Tensor | None:
@@ -641,30 +735,14 @@ def _match_probe(jt: JoinType, filter: "CompareFilter | None", build_side_record
     (get_semi_indices / get_anti_indices) from the matched-probe bitmap. Without a filter on
     one Int32/Int64 key: HashTable.probe_match as is. Else the filtered match probe, under the
     predicate _apply_filter would build, plus the key equalities of a composite key."""
-    n = probe_batch.num_rows
     left = jt in (JoinType.LeftSemi, JoinType.LeftAnti)
     flags = build_visited if left else None
-    simple = _simple_match_key(lookup, key_cols)
-    if simple:
-        k = key_cols[0]
-        keys, valid, voff = k.key_tensor(), k.valid, k.voff
-    else:
-        (keys, valid), voff = composite_keys(key_cols), 0
-    if simple and filter is None:
+    keys, valid, voff, pred = _probe_keys_and_predicate(filter, build_side_records, lookup, probe_batch, probe_cols,
+                                                        key_cols)
+    n = probe_batch.num_rows
+    if pred is None:
         m = lookup.table.probe_match(keys, valid, valid_offset=voff, build_flags=flags)
     else:
-        build_cols = lookup.build_columns(build_side_records)
-        bnames, nb = list(build_side_records.schema.names), build_side_records.num_rows
-        eq = []
-        if not simple:
-            sh = lookup._shared
-            eq = [(build_cols[e if isinstance(e, int) else build_side_records.schema.get_field_index(e)], k)
-                  for e, k in zip(sh.key_exprs, key_cols)]
-        if filter is not None:
-            pred = filter.predicate(build_cols, bnames, probe_cols, list(probe_batch.schema.names), nb, n, eq_keys=eq)
-        else:
-            pred = PairPredicate([b for b, _ in eq], [p for _, p in eq],
-                                 [(("build", i), "==", ("probe", i)) for i in range(len(eq))], nb, n)
         m = lookup.table.probe_match(keys, valid, valid_offset=voff, build_flags=flags, predicate=pred,
                                      bitmap=not left)
     if left:
@@ -700,6 +778,17 @@ def probe_batch(join_type: JoinType, probe_expressions: Sequence[str | int], bui
         if rows is None:
             return None
         return _batch([c.take(rows) for c in probe_cols], list(probe_batch.schema.names))
+    if _takes_filtered_path(jt, filter, lookup, key_cols, n, build_side_records):
+        # only the passing pairs are written; marks and the unmatched probe rows come from the plan
+        plan = _filtered_plan(jt, filter, build_side_records, lookup, probe_batch, probe_cols, key_cols, build_visited)
+        b, p = plan.all()
+        if jt in (JoinType.Right, JoinType.Full):
+            unmatched = select_bitmap(plan.bitmap, n, 0)
+            b = torch.cat([b, torch.full((unmatched.numel(),), -1, dtype=torch.int64, device=dev)])
+            p = torch.cat([p, unmatched])
+        build_cols = lookup.build_columns(build_side_records)
+        return _batch([c.take(b) for c in build_cols] + [c.take(p) for c in probe_cols],
+                      list(build_side_records.schema.names) + list(probe_batch.schema.names))
     b, p = lookup.matching_indices_device(key_cols, build_side_records)
     build_cols = lookup.build_columns(build_side_records)
     bnames, pnames = list(build_side_records.schema.names), list(probe_batch.schema.names)
@@ -749,6 +838,22 @@ def _probe_batch_windowed(jt: JoinType, filter: "JoinFilter | CompareFilter | No
     bnames = list(build_side_records.schema.names)
     emits_pairs = jt in (JoinType.Inner, JoinType.Left, JoinType.Right, JoinType.Full)
     probe_side = jt in (JoinType.Right, JoinType.Full, JoinType.RightSemi, JoinType.RightAnti)
+    if _takes_filtered_path(jt, filter, lookup, key_cols, n, build_side_records):
+        # windows of passing pairs: every batch has up to `limit` of them, none is empty
+        plan = _filtered_plan(jt, filter, build_side_records, lookup, probe_batch, probe_cols, key_cols, build_visited)
+        out = [_batch([c.take(b) for c in build_cols] + [c.take(p) for c in probe_cols], bnames + pnames)
+               for b, p in plan.windows(limit)]
+        if jt in (JoinType.Right, JoinType.Full):
+            unmatched = select_bitmap(plan.bitmap, n, 0)
+            for r in _row_chunks(unmatched, limit) if unmatched.numel() else []:
+                nulls = torch.full((r.numel(),), -1, dtype=torch.int64, device=dev)
+                out.append(_batch([c.take(nulls) for c in build_cols] + [c.take(r) for c in probe_cols],
+                                  bnames + pnames))
+        if not out:  # no row at all: the empty batch the unbounded path returns
+            e_b = torch.empty(0, dtype=torch.int64, device=dev)
+            e_p = torch.empty(0, dtype=torch.int32, device=dev)
+            out.append(_batch([c.take(e_b) for c in build_cols] + [c.take(e_p) for c in probe_cols], bnames + pnames))
+        return out
     probe_flags = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev) if probe_side else None
     out = []
     for b, p in lookup.matching_windows(key_cols, limit, build_side_records):
@@ -892,7 +997,8 @@ class ParallelHashJoin:
                  on: Sequence[tuple[str, str]], join_type: JoinType | str = JoinType.Inner, device: int = 0,
                  replacement: JoinReplacement = JoinReplacement.Gpu, filter: "JoinFilter | CompareFilter | None" = None,
                  right_schema: pa.Schema | None = None, devices: Sequence[int] | None = None, plan: str = "auto",
-                 prefilter: bool = False, match_probe: bool = False, max_output_rows: int | None = None):
+                 prefilter: bool = False, match_probe: bool = False, max_output_rows: int | None = None,
+                 filtered_probe: bool = False):
         """max_output_rows: None, or the most rows any output batch, pair buffer or gathered
         column may have (BuildImplementation; same rows in the same order, in more batches;
         not with `devices=`);
@@ -901,7 +1007,10 @@ class ParallelHashJoin:
         match_probe: semi and anti joins on one device, without a filter or under a
         CompareFilter, probe for matches instead of pairs (BuildImplementation; same output;
         the match path ignores the key filter; a callable JoinFilter, float / decimal key
-        columns and other joins silently take the pair path)."""
+        columns and other joins silently take the pair path);
+        filtered_probe: Inner / Left / Right / Full joins on one device under a CompareFilter,
+        or on a composite key, write only the pairs that pass (BuildImplementation; same
+        output; ignores the key filter; the other cases silently take the pair path)."""
         if len(on) < 1:
             raise HjError(HJ_ERR_INVALID, "an equi-join needs at least one (left, right) key pair")
         self.join_type = JoinType.parse(join_type)
@@ -914,7 +1023,7 @@ class ParallelHashJoin:
         self.right_schema = right_schema or next((b.schema for part in self.right for b in part), None)
         self._build = BuildImplementation(replacement, n, device=device, devices=devices, plan=plan,
                                           prefilter=prefilter, match_probe=match_probe,
-                                          max_output_rows=max_output_rows)
+                                          max_output_rows=max_output_rows, filtered_probe=filtered_probe)
         self._finalizer = _Finalizer(n)
 
     def execute(self, partition: int) -> list[pa.RecordBatch]:

@@ -193,6 +193,60 @@ class PairPlan:
             yield self.window(lo, max_pairs)
 
 
+class FilteredPairPlan(PairPlan):
+    """Result of HashTable.pair_plan(predicate=...): the pairs of one probe call that pass the
+    predicate (F), in windows of the canonical order; no candidate pair is ever written.
+    `total` (|F|), `candidates` (|S|, the equi-join's fan-out) and `matched` (probe rows with
+    a pair in F) read the statistics once, lazily: the only host synchronisation. `bitmap`:
+    the matched-probe bitmap over F (uint8 device tensor, as MatchResult.bitmap) when asked
+    for, else None. The plan keeps the predicate, and with it the column buffers, alive."""
+
+    def __init__(self, table: "HashTable", n: int, plan: torch.Tensor, d_stats: torch.Tensor,
+                 probe_ids: torch.Tensor | None, probe_base: int, predicate, bitmap: torch.Tensor | None):
+        super().__init__(table, n, plan, d_stats, probe_ids, probe_base)
+        self._pred, self.bitmap, self._stats = predicate, bitmap, None
+
+    def _read(self) -> tuple:
+        if self._stats is None:
+            self._stats = tuple(int(v) for v in self._d_total.cpu().tolist())
+        return self._stats
+
+    @property
+    def matched(self) -> int:
+        """Probe rows with a pair in F (set bits of the bitmap)."""
+        return self._read()[0]
+
+    @property
+    def total(self) -> int:
+        """|F|: the pairs that pass the predicate (may exceed 2^32)."""
+        return self._read()[1]
+
+    @property
+    def candidates(self) -> int:
+        """|S|: the pairs of the probe before the predicate."""
+        return self._read()[2]
+
+    def window(self, lo: int, cap: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """Pairs [lo, lo + cap) of F as device tensors (build int64, probe int32) of exactly
+        w = clamp(total - lo, 0, cap) elements."""
+        if lo < 0 or cap < 0:
+            raise ValueError("lo and cap must not be negative")
+        w = max(min(self.total - lo, cap), 0)
+        dev = self._plan.device
+        ob = torch.empty(w, dtype=torch.int64, device=dev)
+        op = torch.empty(w, dtype=torch.int32, device=dev)
+        if w:
+            self._table.pair_window_filtered_async(self._plan.data_ptr(), self.n, self._pred, lo, w, ob.data_ptr(),
+                                                   op.data_ptr(), torch.cuda.current_stream(dev).cuda_stream,
+                                                   probe_ids_ptr=None if self._ids is None else self._ids.data_ptr(),
+                                                   probe_base=self._base)
+        return ob, op
+
+    def all(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """Every pair of F: window(0, total)."""
+        return self.window(0, self.total)
+
+
 class HashTable:
     """One shared build table for `parallelism` partitions (hj_build_begin .. finish)."""
 
@@ -515,8 +569,53 @@ class HashTable:
         check(self._L.hj_pair_window(self._h, plan_ptr, n, probe_ids_ptr, probe_base, pair_lo, capacity,
                                      out_build_ptr, out_probe_ptr, d_written_ptr, stream or None), self._L)
 
+    # -- filtered pair plan (hj_pair_plan_filtered, hj_pair_window_filtered) ----------------
+    def pair_plan_filtered_bytes(self, n: int) -> int:
+        """hj_pair_plan_filtered_bytes (no device work)."""
+        v = self._L.hj_pair_plan_filtered_bytes(self._h, int(n))
+        if v < 0:
+            check(_lib.HJ_ERR_INVALID, self._L)
+        return v
+
+    def pair_plan_filtered_async(self, keys_ptr: int, n: int, predicate, plan_ptr: int, stream: int = 0,
+                                 valid_ptr: int | None = None, voff: int = 0, bitmap_ptr: int | None = None,
+                                 build_flags_ptr: int | None = None, nflags: int = 0,
+                                 d_stats_ptr: int | None = None) -> None:
+        """hj_pair_plan_filtered on raw device pointers (no sync, no allocation); predicate: a
+        columns.PairPredicate; d_stats: an int64[3]."""
+        check(self._L.hj_pair_plan_filtered(self._h, keys_ptr or None, valid_ptr, voff, n, predicate.struct, plan_ptr,
+                                            bitmap_ptr, build_flags_ptr, nflags, d_stats_ptr, stream or None), self._L)
+
+    def pair_window_filtered_async(self, plan_ptr: int, n: int, predicate, pair_lo: int, capacity: int,
+                                   out_build_ptr: int | None, out_probe_ptr: int | None, stream: int = 0,
+                                   d_written_ptr: int | None = None, probe_ids_ptr: int | None = None,
+                                   probe_base: int = 0) -> None:
+        """hj_pair_window_filtered on raw device pointers (no sync, no allocation): passing
+        pairs [pair_lo, pair_lo + capacity) of the filtered plan of n rows, under the predicate
+        the plan was made with; probe_idx = row, probe_ids[row] or probe_base + row."""
+        if probe_ids_ptr is not None and probe_base:
+            raise ValueError("probe_ids_ptr and probe_base are exclusive: add the base to the ids")
+        check(self._L.hj_pair_window_filtered(self._h, plan_ptr, n, predicate.struct, probe_ids_ptr, probe_base,
+                                              pair_lo, capacity, out_build_ptr, out_probe_ptr, d_written_ptr,
+                                              stream or None), self._L)
+
+    def _pair_plan_filtered(self, ki: KeyInput, dev, probe_ids, probe_base: int, predicate,
+                            build_flags: torch.Tensor | None, bitmap: bool) -> "FilteredPairPlan":
+        n = ki.n
+        plan = torch.empty(self.pair_plan_filtered_bytes(n), dtype=torch.uint8, device=dev)
+        bm = torch.empty(((n + 63) // 64) * 8, dtype=torch.uint8, device=dev) if bitmap else None
+        d_stats = torch.empty(3, dtype=torch.int64, device=dev)
+        self.pair_plan_filtered_async(ki.ptr, n, predicate, plan.data_ptr(),
+                                      torch.cuda.current_stream(dev).cuda_stream, ki.valid_ptr, ki.voff,
+                                      None if bm is None else bm.data_ptr(),
+                                      None if build_flags is None else build_flags.data_ptr(),
+                                      0 if build_flags is None else build_flags.numel(), d_stats.data_ptr())
+        # the key tensors are released in stream order by torch's allocator; the plan keeps the predicate
+        return FilteredPairPlan(self, n, plan, d_stats, probe_ids, probe_base, predicate, bm)
+
     def pair_plan(self, keys: torch.Tensor, valid=None, valid_offset: int = 0, probe_ids: torch.Tensor | None = None,
-                  probe_base: int = 0, prefilter=None) -> "PairPlan":
+                  probe_base: int = 0, prefilter=None, predicate=None, build_flags: torch.Tensor | None = None,
+                  bitmap: bool = False) -> "PairPlan":
         """Look every probe row up once and return a PairPlan, whose windows give the pairs
         probe(keys, valid, device_output=True) would return, in the same order, in slices of
         a size the caller chooses: peak memory is the window's, not the join's fan-out. keys:
@@ -526,9 +625,24 @@ class HashTable:
         keys; the rows it rejects are dropped before the plan (they have no pairs), the
         windows name the surviving rows by their ids. Not for a multi-GPU table
         (HJ_ERR_INVALID). No host synchronisation here: PairPlan.total reads the pair count
-        lazily. Plan and windows run on torch's current stream."""
+        lazily. Plan and windows run on torch's current stream.
+        predicate: a columns.PairPredicate over the build side's columns and this batch's (row
+        i of a probe column belongs to keys[i], whatever probe_ids says): the result is a
+        FilteredPairPlan, whose windows hold only the pairs that pass it, in the same order
+        (hj_pair_plan_filtered: the candidates are evaluated in registers, none is written).
+        With it, build_flags (a uint8 device tensor, one byte per build row or id, OR'ed in
+        place) marks the build rows of the passing pairs and bitmap=True asks for the
+        matched-probe bitmap over them - an outer join's bookkeeping from the same walk. The
+        key filter is not used under a predicate (prefilter must be None)."""
         if not (isinstance(keys, torch.Tensor) and keys.is_cuda):
             raise TypeError("pair_plan takes a device tensor of keys")
+        if predicate is None and (build_flags is not None or bitmap):
+            raise ValueError("build_flags and bitmap belong to a filtered plan: give a predicate")
+        if predicate is not None and prefilter is not None:
+            raise ValueError("the filtered pair plan does not use a key filter")
+        if build_flags is not None and not (build_flags.is_cuda and build_flags.dtype == torch.uint8 and
+                                            build_flags.is_contiguous()):
+            raise TypeError("build_flags must be a contiguous uint8 device tensor")
         if probe_ids is not None and probe_base:
             raise ValueError("probe_ids and probe_base are exclusive: add the base to the ids")
         if probe_ids is not None and not (probe_ids.is_cuda and probe_ids.dtype == torch.int32 and
@@ -538,6 +652,8 @@ class HashTable:
         if ki.n and ki.key_type != self.key_type:
             raise TypeError("probe key type differs from the build key type")
         dev = keys.device
+        if predicate is not None:
+            return self._pair_plan_filtered(ki, dev, probe_ids, probe_base, predicate, build_flags, bitmap)
         if prefilter is not None:
             if prefilter.device != (dev.index or 0):
                 raise ValueError("the prefilter lives on another device than the probe keys")

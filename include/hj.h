@@ -427,6 +427,83 @@ hj_status hj_pair_window(const hj_table* t, const void* plan, int64_t n,
                          uint64_t* out_build, uint32_t* out_probe, int64_t* d_written,
                          void* stream);
 
+/* Filtered pair plan: a pair plan under a join filter, whose windows hold only the pairs
+ * that pass it. Replaces get_matching_indices (src/shared/shared.rs:29-47) followed by
+ * apply_join_filter_to_indices (src/shared/datafusion_private.rs:295-328) inside
+ * lookup_inner_join_probe_batch (src/operator/probe_lookup_implementation/inner.rs:79-129);
+ * the filter runs before any marking, as in full.rs:140-175. The reference materialises every
+ * candidate pair of the equi-join, gathers their rows and then keeps the passing ones; here
+ * the candidates are evaluated in registers, twice (count, then write), and only the passing
+ * pairs reach memory. All three entry points below replace that pair of reference calls.
+ * Opt-in: nothing else in the library calls these. Device pointers,
+ * asynchronous on `stream`, no host synchronisation, no allocation.
+ *
+ * S, F and the pair pass rule are exactly hj_probe_match_filtered's: S is the pairs
+ * hj_probe_async would produce for the same table, keys, validity and n at unlimited
+ * capacity (probe_idx = row), F the subsequence of S that passes `pred`, in S's canonical
+ * order (probe rows ascending, each row's build rows descending). With explicit build ids the
+ * id is the pair's build_idx and also the row of the build columns; an id >= build_rows
+ * fails unread. Row i of a probe column belongs to key i.
+ *
+ * hj_pair_plan_filtered evaluates every
+ * candidate of every row once - no first-pass exit and no flag skip: the counts are exact -
+ * and leaves in `plan` what the windows need; the layout is opaque. `plan`: caller-owned
+ * device memory, 8-byte aligned, hj_pair_plan_filtered_bytes(t, n) bytes; the call's scratch
+ * lives inside it.
+ *   out_bitmap, build_flags / nflags (each optional): exactly as hj_probe_match_filtered
+ *                defines them over F. Bitmap words are written whole, bits at and beyond n
+ *                are 0, no pre-zeroing. Flags are OR'ed into arbitrary prior contents, only
+ *                ever stored 1, ids >= nflags are skipped.
+ *   d_stats      (optional) device int64[3], overwritten, all three always written:
+ *                [0] probe rows with a pair in F, [1] |F|, [2] |S|. |F| and |S| may exceed
+ *                2^32.
+ * The launches: the count walk and one scan of the block totals (one workgroup), after a
+ * 64-byte memset; no workgroup waits on another. Once the call has run the plan is
+ * read-only and does not depend on the key and validity buffers. It does depend on the table
+ * and on the predicate's column buffers, which must stay unchanged until the last window has
+ * run.
+ *
+ * hj_pair_window_filtered writes
+ * F[pair_lo + i] to out_build[i] / out_probe[i] for 0 <= i < w, w = clamp(|F| - pair_lo, 0,
+ * capacity), and *d_written (optional device int64) = w. Nothing at or beyond index w is
+ * written. out_probe is probe_ids[row] when probe_ids (u32[n]) is given, else probe_base +
+ * row, as in hj_pair_window; both together are HJ_ERR_INVALID. The rows of the predicate's
+ * probe columns are always the batch's rows, never the ids. `n` is the plan's, and `pred`
+ * must be the predicate the plan was made with, over unchanged columns: the library checks
+ * only that the predicate is valid and pred->probe_rows >= n; the rest is the caller's
+ * contract (a different predicate never writes outside [0, w), but the pairs are then
+ * unspecified). Cost: one range test per block of 1024 rows, plus the candidates of the
+ * rows whose passing pairs intersect the window; rows without a pair in F are never walked
+ * again. Any number of windows of one plan may run concurrently on different streams; the
+ * caller orders them after the plan as for any buffer.
+ *
+ * hj_pair_plan_filtered_bytes: the plan's size, no
+ * device work; -1 for a table the calls reject or n outside [0, 2^32).
+ *
+ * Both calls order themselves after the build, and hj_table_free waits for them. Tables:
+ * every one-device table hj_probe_match accepts (direct-addressed plain, packed and run
+ * refs, hashed, hj_table_wrap_dense, explicit ids with or without HJ_IDS_U31); a multi-GPU
+ * table returns HJ_ERR_INVALID. n in [0, 2^32); n == 0 is valid and still writes d_stats /
+ * d_written. pair_lo >= 0, 0 <= capacity <= 2^42. Errors, in this order:
+ * hj_pair_predicate_check's (an invalid predicate is HJ_ERR_INVALID, with a message that
+ * names the term, on a machine without a GPU too); a null, unbuilt, failed or multi-GPU
+ * table, n, pair_lo or capacity out of range, null keys, bad nflags, probe_ids together with
+ * probe_base, as hj_probe_match_filtered and hj_pair_window; a null or misaligned plan, a
+ * misaligned out_bitmap, d_stats, d_written, out_build (8 bytes) or out_probe (4); a null
+ * output with capacity > 0; pred->probe_rows < n: HJ_ERR_INVALID. */
+int64_t hj_pair_plan_filtered_bytes(const hj_table* t, int64_t n);
+hj_status hj_pair_plan_filtered(const hj_table* t, const void* keys, const uint8_t* validity,
+                                int64_t validity_offset, int64_t n,
+                                const struct hj_pair_predicate* pred, void* plan,
+                                uint8_t* out_bitmap, uint8_t* build_flags, int64_t nflags,
+                                int64_t* d_stats, void* stream);
+hj_status hj_pair_window_filtered(const hj_table* t, const void* plan, int64_t n,
+                                  const struct hj_pair_predicate* pred,
+                                  const uint32_t* probe_ids, uint32_t probe_base,
+                                  int64_t pair_lo, int64_t capacity,
+                                  uint64_t* out_build, uint32_t* out_probe,
+                                  int64_t* d_written, void* stream);
+
 /* Probe strategy for later probes of this process: 0 auto (sliced for tables past the L2s
  * - more than 2^20 key values or 2^16 buckets, at most 4 passes of 2047 slices - with a
  * probe side at least as large as the key range / bucket count, else fused),
