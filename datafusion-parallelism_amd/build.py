@@ -25,10 +25,10 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 ARCH = "gfx950"
 
 SOURCES_HIP = ["hj_kernels.hip", "hj_columns.hip", "hj_keys.hip", "hj_filter.hip", "hj_window.hip",
-               "hj_pairfilter.hip"]
+               "hj_pairfilter.hip", "hj_match.hip"]
 SOURCES_CPP = ["hj_api.cpp", "hj_dist.cpp"]
 HEADERS = ["hj_device.h", "hj_launch.h", "hj_util.h", "hj_compact.h", "hj_host.h", "hj_comm.h",
-           "hj_pairpred.h"]
+           "hj_pairpred.h", "hj_lookup.h"]
 # test library: the product objects + the in-process thread transport for hj_comm
 # (tests/test_gpu_dist_threads.py); never part of libdfp_hj.so
 COMMTEST_LIB = os.path.join(LIBDIR, "libdfp_hj_commtest.so")

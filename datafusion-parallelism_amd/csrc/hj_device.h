@@ -1,4 +1,4 @@
-// hj_device.h — data layout shared by the gfx950 kernels (hj_kernels.hip) and the
+// hj_device.h — data layout shared by the gfx950 kernels (hj_kernels.hip, hj_match.hip) and the
 // C-ABI host layer (hj_api.cpp).
 //
 // Slot table in HBM:

@@ -36,7 +36,7 @@
 
 #include "hj_device.h"
 #include "hj_launch.h"
-#include "hj_pairpred.h"
+#include "hj_lookup.h"
 #include "hj_util.h"
 
 namespace dfp {
@@ -62,12 +62,11 @@ __device__ __forceinline__ int find_seg(const Segment* segs, int nseg, int64_t r
     return lo;
 }
 
-// home bucket of a key (its probe sequence never leaves the bucket's chunk), and of its
-// stored form (no rehash)
+// home bucket of a key (its probe sequence never leaves the bucket's chunk); of its stored
+// form: stored_bucket (hj_lookup.h)
 __device__ __forceinline__ uint32_t home_bucket(int64_t key, uint32_t nb) {
     return bucket_of(mix64((uint64_t)key), nb);
 }
-__device__ __forceinline__ uint32_t stored_bucket(unsigned long long sk, uint32_t nb) { return bucket_of(sk, nb); }
 
 // ---------------------------------------------------------------------------
 // build 1: rows -> chunk order in two partition levels. A 32 K-row tile spread over all
@@ -945,142 +944,6 @@ dup_sort_big_kernel(uint32_t* dup_rows, const BigSeg* __restrict__ big, const Bu
 constexpr int kProbeThreads = 256;
 constexpr int kGroups = 4;                                 // 4 groups x 1024 rows
 constexpr int kProbeTile = kProbeThreads * 4 * kGroups;   // 4096 probe rows per tile
-
-typedef long long v2i64 __attribute__((ext_vector_type(2)));
-
-template <typename K, bool NT = false>
-__device__ __forceinline__ void load4(const void* keys, int64_t row0, int64_t n, bool vec, int64_t (&k)[4]) {
-    const K* kp = reinterpret_cast<const K*>(keys);
-    if (vec && row0 + 4 <= n) {
-        if constexpr (sizeof(K) == 8) {
-            const v2i64* p = reinterpret_cast<const v2i64*>(kp + row0);
-            v2i64 a, b;
-            if constexpr (NT) {
-                a = __builtin_nontemporal_load(p);
-                b = __builtin_nontemporal_load(p + 1);
-            } else {
-                a = p[0];
-                b = p[1];
-            }
-            k[0] = a.x; k[1] = a.y; k[2] = b.x; k[3] = b.y;
-        } else {
-            const int4 a = *reinterpret_cast<const int4*>(kp + row0);
-            k[0] = a.x; k[1] = a.y; k[2] = a.z; k[3] = a.w;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) k[q] = (row0 + q < n) ? (int64_t)kp[row0 + q] : 0;
-    }
-}
-
-// count of build rows behind a match ref
-__device__ __forceinline__ uint32_t ref_count(const uint32_t* dup_rows, uint32_t ref, uint32_t off_mask) {
-    const uint32_t c = ref_count_inline(ref, off_mask);
-    return c == kCountUnknown ? dup_rows[ref & off_mask] : c;
-}
-
-// One bucket line: ref of `sk` if present, else kMiss; *more = the line is full, does
-// not hold the key, and some insert passed it (meta bit 0): look at the next bucket of
-// the chunk. Slots fill in order and are never freed, so an empty slot ends a key's probe
-// sequence, and so does a full bucket that no insert ever passed. Branch-free.
-__device__ __forceinline__ uint32_t scan_line(const uint4& a0, const uint4& a1, const uint4& a2, const uint4& a3,
-                                              unsigned long long sk, bool* more, uint32_t* cnt) {
-    const unsigned long long k0 = ((unsigned long long)a0.y << 32) | a0.x;
-    const unsigned long long k1 = ((unsigned long long)a0.w << 32) | a0.z;
-    const unsigned long long k2 = ((unsigned long long)a1.y << 32) | a1.x;
-    const unsigned long long k3 = ((unsigned long long)a1.w << 32) | a1.z;
-    const unsigned long long k4 = ((unsigned long long)a2.y << 32) | a2.x;
-    const bool e0 = k0 == sk, e1 = k1 == sk, e2 = k2 == sk, e3 = k3 == sk, e4 = k4 == sk;
-    const bool z = (k0 == 0) | (k1 == 0) | (k2 == 0) | (k3 == 0) | (k4 == 0);
-    uint32_t ref = e4 ? a3.z : kMiss;
-    ref = e3 ? a3.y : ref;
-    ref = e2 ? a3.x : ref;
-    ref = e1 ? a2.w : ref;
-    ref = e0 ? a2.z : ref;
-    *more = (ref == kMiss) & !z & ((a3.w & 1u) != 0);
-    // row count: 0 miss, 1 single row, the inline meta count of a duplicated key, or
-    // kCountUnknown (read dup_rows[off])
-    const uint32_t m = a3.w;
-    uint32_t c = e4 ? (m >> 25) : 0u;
-    c = e3 ? (m >> 19) : c;
-    c = e2 ? (m >> 13) : c;
-    c = e1 ? (m >> 7) : c;
-    c = e0 ? (m >> 1) : c;
-    c &= 63u;
-    *cnt = ref == kMiss ? 0u : (!(ref & kDupFlag) ? 1u : (c ? c : kCountUnknown));
-    return ref;
-}
-
-// Refs of the four probe rows row0..row0+3 (kMiss: no match, null, or past n).
-template <typename K, bool HAS_VALID, bool NT = false>
-__device__ __forceinline__ void lookup4(const TableView& tv, const void* __restrict__ keys,
-                                        const uint8_t* __restrict__ valid, int64_t voff, int64_t n, bool vec,
-                                        int64_t row0, uint32_t (&ref)[4], uint32_t (&cnt)[4]) {
-    if (tv.dense != nullptr) {  // direct-addressed table: range check + one 4-byte read per row
-        int64_t k[4];
-        load4<K, NT>(keys, row0, n, vec, k);
-        uint32_t r[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool in = (row0 + q < n) && (!HAS_VALID || bit_valid(valid, voff, row0 + q));
-            const uint64_t idx = (uint64_t)k[q] - (uint64_t)tv.dmin;
-            r[q] = (in && idx < tv.drange) ? tv.dense[idx] : kMiss;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            ref[q] = r[q];
-            // packed dense refs carry counts <= 15 (or a run) in bits 24-30 (kPackedMask tables)
-            cnt[q] = ref_count_inline(r[q], tv.off_mask);
-        }
-        return;
-    }
-    const Bucket* __restrict__ tbl = tv.tbl;
-    const uint32_t cmask = (1u << tv.clog2) - 1;
-    int64_t k[4];
-    load4<K, NT>(keys, row0, n, vec, k);
-    bool in[4];
-    unsigned long long sk[4];
-    uint32_t b[4];
-    uint4 L0[4], L1[4], L2[4], L3[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        in[q] = (row0 + q < n) && (!HAS_VALID || bit_valid(valid, voff, row0 + q));
-        sk[q] = stored_key(k[q]);
-        b[q] = (in[q] && sk[q] != 0) ? stored_bucket(sk[q], tv.nb) : tv.nb;
-    }
-    // issue the 64-byte bucket line of all four rows before any compare (MLP)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint4* p = reinterpret_cast<const uint4*>(tbl + b[q]);
-        L0[q] = p[0]; L1[q] = p[1]; L2[q] = p[2]; L3[q] = p[3];
-    }
-    bool more[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        ref[q] = scan_line(L0[q], L1[q], L2[q], L3[q], sk[q], &more[q], &cnt[q]);
-        if (sk[q] == 0) {  // key 0: the side bucket (ref[0] = word 10, meta = word 15 = rows)
-            ref[q] = L3[q].w ? L2[q].z : kMiss;
-            cnt[q] = L3[q].w;
-            more[q] = false;
-        }
-        if (!in[q]) { ref[q] = kMiss; cnt[q] = 0; more[q] = false; }
-    }
-    // rare: the home line is full and does not hold the key
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        uint32_t bb = b[q];
-        for (uint32_t probes = 0; more[q] && probes < cmask; ++probes) {
-            bb = (bb & ~cmask) | ((bb + 1) & cmask);
-            const uint4* p = reinterpret_cast<const uint4*>(tbl + bb);
-            ref[q] = scan_line(p[0], p[1], p[2], p[3], sk[q], &more[q], &cnt[q]);
-        }
-    }
-}
-
-__device__ __forceinline__ uint32_t resolve_count(const uint32_t* dup_rows, uint32_t ref, uint32_t cnt,
-                                                  uint32_t off_mask) {
-    return cnt == kCountUnknown ? dup_rows[ref & off_mask] : cnt;
-}
 
 // Writes the pairs of four probe rows starting at output position `pos` (canonical:
 // rows ascending, each row's build rows descending = the order of its dup segment).
@@ -5009,870 +4872,6 @@ hipError_t launch_probe(int key_bytes, const TableView& tv, const void* keys, co
     }
 #undef DFP_FUSED_K
 #undef DFP_FUSED
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// match probe: per probe row whether, and how often, its key occurs in the table; no
-// pairs. The lookup of the pair probe (lookup4), stopped before the emission: what the
-// reference's semi and anti joins keep of get_matching_indices once get_semi_indices /
-// get_anti_indices and ConcurrentBitSet::set_ones have folded the pairs into flags
-// (src/operator/probe_lookup_implementation/right_semi.rs:74-125, left_semi.rs:112-164,
-// src/shared/datafusion_private.rs:85-135). One launch: lookup, counts, bitmap words, build
-// marks, statistics. No look-back, scan or ordering: a grid-stride loop over blocks of
-// kMatchRows rows.
-//
-// Bitmap layout. lookup4 gives a lane four consecutive rows (one 16- or 32-byte key load,
-// four bucket lines in flight per lane before the first compare), so a wave covers 256
-// rows = four bitmap words, and the lane's four match bits are a nibble of one of them.
-// The kernel keeps lookup4 - its memory-level parallelism is what a random table read
-// lives on - and assembles the words from four ballots (ballot q: bit L = row 4L + q):
-// word w = the bits 16w..16w+15 of each ballot spread to every fourth bit, OR'ed at shift
-// q. That is ~20 scalar-uniform ALU operations per 256 rows in lanes 0-3, against a
-// reload of the keys in ballot order (filter_test_kernel's layout) that would give up the
-// vector key load and three of the four lines in flight.
-//
-// Build marks (MARK). Singles and keys of <= kRunMaxRows rows (every run ref among them)
-// are marked directly: <= 9 byte stores per probe row. A larger key is claimed once per
-// call by an atomic OR into the call's own zeroed claim bitmap - indexed by the key's
-// position in a direct-addressed table, by its duplicate-segment offset / 8 in a hashed
-// one (segments of >= 10 rows are >= 11 words apart) - and only the claimer walks its
-// segment: by itself up to 64 rows, with the whole wave beyond. m probe rows of a key of c
-// rows so cost m claim tests + c stores, not m * c. The flags themselves are never the
-// claim: they may hold anything before the call, and are only ever stored 1.
-// ---------------------------------------------------------------------------
-constexpr int kMatchThreads = 256;
-constexpr int kMatchRows = kMatchThreads * 4;  // rows of one block iteration (16 bitmap words)
-constexpr int kMatchMaxBlocks = 2048;
-constexpr uint32_t kMatchLaneWalk = 64;        // a claimed segment beyond this is walked by the wave
-
-// bit j of the low 16 bits -> bit 4j
-__device__ __forceinline__ unsigned long long spread16_by4(unsigned long long x) {
-    x &= 0xFFFFull;
-    x = (x | (x << 24)) & 0x000000FF000000FFull;
-    x = (x | (x << 12)) & 0x000F000F000F000Full;
-    x = (x | (x << 6)) & 0x0303030303030303ull;
-    x = (x | (x << 3)) & 0x1111111111111111ull;
-    return x;
-}
-
-__device__ __forceinline__ void match_mark(const TableView& tv, uint32_t row, uint8_t* __restrict__ flags,
-                                           uint64_t nflags) {
-    const uint64_t id = tv.row_ids != nullptr ? tv.row_ids[row] : (uint64_t)row;
-    if (id < nflags) flags[id] = 1;  // idempotent byte stores: no atomics needed
-}
-
-// COUNTS and MARK select the optional outputs at compile time (the marking's registers and
-// the count stores leave the other instantiations); the bitmap's presence is a wave-uniform
-// test of its pointer around four ballots and one store, not worth doubling the variants.
-template <typename K, bool HAS_VALID, bool COUNTS, bool MARK>
-__global__ void __launch_bounds__(kMatchThreads)
-probe_match_kernel(TableView tv, const void* __restrict__ keys, const uint8_t* __restrict__ valid, int64_t voff,
-                   int64_t n, bool vec, unsigned long long* __restrict__ out_bitmap, uint32_t* __restrict__ out_counts,
-                   bool cvec, uint8_t* __restrict__ flags, uint64_t nflags, uint32_t* __restrict__ claim,
-                   unsigned long long* __restrict__ stats) {
-    __shared__ unsigned long long s_m[kMatchThreads / 64], s_p[kMatchThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t nwords = (n + 63) >> 6;
-    unsigned long long matched = 0, pairs = 0;
-    for (int64_t blk0 = (int64_t)blockIdx.x * kMatchRows; blk0 < n; blk0 += (int64_t)gridDim.x * kMatchRows) {
-        const int64_t wrow0 = blk0 + (int64_t)wave * 256;
-        if (wrow0 >= n) continue;  // the whole wave: no word of the bitmap starts here
-        const int64_t row0 = wrow0 + (int64_t)lane * 4;
-        uint32_t ref[4] = {kMiss, kMiss, kMiss, kMiss}, cnt[4] = {0, 0, 0, 0};
-        if (row0 < n) lookup4<K, HAS_VALID>(tv, keys, valid, voff, n, vec, row0, ref, cnt);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            cnt[q] = resolve_count(tv.dup_rows, ref[q], cnt[q], tv.off_mask);
-            matched += ref[q] != kMiss;
-            pairs += cnt[q];
-        }
-        if (out_bitmap != nullptr) {
-            unsigned long long b[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) b[q] = __ballot(ref[q] != kMiss);
-            if (lane < 4) {  // lane w assembles word w of the wave's four
-                unsigned long long word = 0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) word |= spread16_by4(b[q] >> (16 * lane)) << q;
-                const int64_t widx = (wrow0 >> 6) + lane;
-                if (widx < nwords) out_bitmap[widx] = word;  // rows >= n are kMiss: tail bits 0
-            }
-        }
-        if constexpr (COUNTS) {
-            if (cvec && row0 + 4 <= n) {
-                *reinterpret_cast<uint4*>(out_counts + row0) = make_uint4(cnt[0], cnt[1], cnt[2], cnt[3]);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (row0 + q < n) out_counts[row0 + q] = cnt[q];
-            }
-        }
-        if constexpr (MARK) {
-            bool big[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t r = ref[q], c = cnt[q];
-                big[q] = false;
-                if (r == kMiss) continue;
-                if (!(r & kDupFlag)) {
-                    match_mark(tv, r, flags, nflags);
-                } else if (c <= kRunMaxRows) {
-                    for (uint32_t j = 0; j < c; ++j)
-                        match_mark(tv, dup_ref_row(tv.dup_rows, r, tv.off_mask, j), flags, nflags);
-                } else {
-                    const uint32_t off = r & tv.off_mask;
-                    uint32_t ci = off >> 3;
-                    if (tv.dense != nullptr)  // a matched row: row0 + q < n and the key is in range
-                        ci = (uint32_t)((uint64_t)(int64_t) reinterpret_cast<const K*>(keys)[row0 + q] -
-                                        (uint64_t)tv.dmin);
-                    uint32_t* w = claim + (ci >> 5);
-                    const uint32_t bit = 1u << (ci & 31);
-                    // most rows of a hot key find it claimed: test before the read-modify-write
-                    bool mine = false;
-                    if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit))
-                        mine = !(atomicOr(w, bit) & bit);
-                    if (mine) {
-                        if (c <= kMatchLaneWalk) {
-                            for (uint32_t j = 0; j < c; ++j) match_mark(tv, tv.dup_rows[off + 1 + j], flags, nflags);
-                        } else {
-                            big[q] = true;
-                        }
-                    }
-                }
-            }
-            // segments of more than kMatchLaneWalk rows: the wave walks them one after another
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                unsigned long long m = __ballot(big[q]);
-                while (m) {
-                    const int src = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    const uint32_t off = __shfl(ref[q] & tv.off_mask, src, 64);
-                    const uint32_t c = __shfl(cnt[q], src, 64);
-                    for (uint32_t j = lane; j < c; j += 64) match_mark(tv, tv.dup_rows[off + 1 + j], flags, nflags);
-                }
-            }
-        }
-    }
-    // statistics: wave reduction, then one atomic pair per workgroup
-    const unsigned long long wm = wave_sum<unsigned long long>(matched);
-    const unsigned long long wp = wave_sum<unsigned long long>(pairs);
-    if (lane == 0) { s_m[wave] = wm; s_p[wave] = wp; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long tm = 0, tp = 0;
-        for (int w = 0; w < kMatchThreads / 64; ++w) { tm += s_m[w]; tp += s_p[w]; }
-        if (tm) atomicAdd(stats, tm);
-        if (tp) atomicAdd(stats + 1, tp);
-    }
-}
-
-int64_t probe_match_workspace(uint64_t claim_bits) {
-    return kMatchWsHeader + (int64_t)((claim_bits + 63) / 64) * 8;
-}
-
-hipError_t launch_probe_match(int key_bytes, const TableView& tv, const void* keys, const uint8_t* valid, int64_t voff,
-                              int64_t n, uint8_t* out_bitmap, uint32_t* out_counts, uint8_t* flags, int64_t nflags,
-                              int64_t* d_stats, void* workspace, uint64_t claim_bits, hipStream_t s) {
-    // workspace: [0, 16) the statistics of a caller that passes none, then the claim bitmap
-    unsigned long long* stats = reinterpret_cast<unsigned long long*>(d_stats != nullptr ? (void*)d_stats : workspace);
-    hipError_t e = hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), s);
-    if (e != hipSuccess) return e;
-    if (n <= 0) return hipSuccess;
-    const bool mark = flags != nullptr && nflags > 0;
-    uint32_t* claim = reinterpret_cast<uint32_t*>((char*)workspace + kMatchWsHeader);
-    if (mark) {
-        e = hipMemsetAsync(claim, 0, (size_t)((claim_bits + 63) / 64) * 8, s);
-        if (e != hipSuccess) return e;
-    }
-    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15) == 0;
-    const bool cvec = (reinterpret_cast<uintptr_t>(out_counts) & 15) == 0;
-    const unsigned grid = (unsigned)std::min<int64_t>((n + kMatchRows - 1) / kMatchRows, kMatchMaxBlocks);
-    unsigned long long* bm = reinterpret_cast<unsigned long long*>(out_bitmap);
-#define DFP_MATCH(KT, HV, CN, MK)                                                                                   \
-    probe_match_kernel<KT, HV, CN, MK><<<grid, kMatchThreads, 0, s>>>(tv, keys, valid, voff, n, vec, bm, out_counts, \
-                                                                      cvec, flags, (uint64_t)nflags, claim, stats)
-#define DFP_MATCH_K(KT, HV)                                          \
-    do {                                                             \
-        if (out_counts && mark) DFP_MATCH(KT, HV, true, true);       \
-        else if (out_counts) DFP_MATCH(KT, HV, true, false);         \
-        else if (mark) DFP_MATCH(KT, HV, false, true);               \
-        else DFP_MATCH(KT, HV, false, false);                        \
-    } while (0)
-    if (key_bytes == 8) {
-        if (valid) DFP_MATCH_K(int64_t, true); else DFP_MATCH_K(int64_t, false);
-    } else {
-        if (valid) DFP_MATCH_K(int32_t, true); else DFP_MATCH_K(int32_t, false);
-    }
-#undef DFP_MATCH_K
-#undef DFP_MATCH
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// filtered match probe: the match probe's outputs over F, the pairs of the probe that pass
-// a pair predicate, in place of all its pairs S. What the reference's semi and anti joins
-// keep once apply_join_filter_to_indices (src/shared/datafusion_private.rs:295-328) has
-// dropped the failing pairs and get_semi_indices / set_ones have folded the rest into flags
-// (right_semi.rs:74-125, left_semi.rs:112-164; the filter runs before any marking,
-// full.rs:140-175). The skeleton is probe_match_kernel's: lookup4, four ballots per bitmap
-// word, one atomic per workgroup and statistic. Between the lookup and the outputs every
-// matched row walks its key's build rows and evaluates the predicate (pf_pair_passes) in
-// registers: no pair is written.
-//
-// The walk. A key of <= kMatchLaneWalk rows is walked by the lane that owns the probe row
-// (a single row: one step). Larger keys are taken by the wave one after another: lane L
-// evaluates candidates L, L + 64, ... and a ballot per round gives the owner the count.
-// The four rows of a lane are taken in a rolled loop (the refs picked by selects on the
-// scalar loop counter), so the predicate's code exists twice per kernel, not eight times.
-//
-// MODE. kMfExists (no counts, no flags): a row's walk stops at its first passing pair - the
-// lane's loop by itself, the wave's rounds on the first non-zero ballot, wave-uniformly.
-// kMfFull: every candidate is evaluated, counted, and its build row marked. With flags as
-// the only output (flags_only) a candidate whose flag reads 1, or whose id the flags do not
-// cover, is skipped unevaluated: flags are only ever stored 1, so a stale 0 costs one
-// evaluation and nothing else. There is no claim bitmap: under a predicate different probe
-// rows of a key pass different build rows.
-// ---------------------------------------------------------------------------
-constexpr int kMfExists = 0, kMfFull = 1;
-
-__device__ __forceinline__ uint32_t mf_sel4(const uint32_t (&a)[4], int q) {
-    return q == 0 ? a[0] : (q == 1 ? a[1] : (q == 2 ? a[2] : a[3]));
-}
-__device__ __forceinline__ void mf_put4(uint32_t (&a)[4], int q, uint32_t v) {
-    a[0] = q == 0 ? v : a[0];
-    a[1] = q == 1 ? v : a[1];
-    a[2] = q == 2 ? v : a[2];
-    a[3] = q == 3 ? v : a[3];
-}
-
-// whether the pair (build row `row`, probe row `prow`) is in F; kMfFull marks it
-template <bool BYTES, int MODE>
-__device__ __forceinline__ bool mf_candidate(const TableView& tv, const PairPred& pr, uint32_t row, uint32_t prow,
-                                             uint8_t* flags, uint64_t nflags, bool flags_only) {
-    const uint64_t id = tv.row_ids != nullptr ? tv.row_ids[row] : (uint64_t)row;
-    if constexpr (MODE == kMfFull) {
-        if (flags_only && (id >= nflags || flags[id] != 0)) return false;  // a racy read: see above
-    }
-    const bool pass = pf_pair_passes<BYTES>(pr, true, id, prow);  // an id >= build_rows fails unread
-    if constexpr (MODE == kMfFull) {
-        if (pass && id < nflags) flags[id] = 1;  // nflags is 0 without flags
-    }
-    return pass;
-}
-
-// stat_mask: bit 0 = stats[0] is asked for, bit 1 = stats[1]; stats[2] always (stats may be null)
-template <typename K, bool HAS_VALID, bool BYTES, int MODE>
-__global__ void __launch_bounds__(kMatchThreads)
-probe_match_filtered_kernel(TableView tv, PairPred pr, const void* __restrict__ keys,
-                            const uint8_t* __restrict__ valid, int64_t voff, int64_t n, bool vec,
-                            unsigned long long* __restrict__ out_bitmap, uint32_t* __restrict__ out_counts, bool cvec,
-                            uint8_t* flags, uint64_t nflags, bool flags_only, unsigned long long* __restrict__ stats,
-                            int stat_mask) {
-    __shared__ unsigned long long s_m[kMatchThreads / 64], s_p[kMatchThreads / 64], s_c[kMatchThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t nwords = (n + 63) >> 6;
-    unsigned long long matched = 0, pairs = 0, cand = 0;
-    for (int64_t blk0 = (int64_t)blockIdx.x * kMatchRows; blk0 < n; blk0 += (int64_t)gridDim.x * kMatchRows) {
-        const int64_t wrow0 = blk0 + (int64_t)wave * 256;
-        if (wrow0 >= n) continue;  // the whole wave: no word of the bitmap starts here
-        const int64_t row0 = wrow0 + (int64_t)lane * 4;
-        uint32_t ref[4] = {kMiss, kMiss, kMiss, kMiss}, cnt[4] = {0, 0, 0, 0};
-        if (row0 < n) lookup4<K, HAS_VALID>(tv, keys, valid, voff, n, vec, row0, ref, cnt);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            cnt[q] = resolve_count(tv.dup_rows, ref[q], cnt[q], tv.off_mask);
-            cand += cnt[q];
-        }
-        // hit[q]: the row's pairs in F (kMfExists: 0 / 1)
-        uint32_t hit[4] = {0, 0, 0, 0};
-#pragma unroll 1
-        for (int q = 0; q < 4; ++q) {  // keys the owning lane walks
-            const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q);
-            uint32_t h = 0;
-            if (c != 0 && c <= kMatchLaneWalk) {  // a matched row: row0 + q < n
-                const uint32_t prow = (uint32_t)(row0 + q);
-                for (uint32_t j = 0; j < c; ++j) {
-                    const uint32_t row = (r & kDupFlag) ? dup_ref_row(tv.dup_rows, r, tv.off_mask, j) : r;
-                    if (mf_candidate<BYTES, MODE>(tv, pr, row, prow, flags, nflags, flags_only)) {
-                        ++h;
-                        if (MODE == kMfExists) break;
-                    }
-                }
-            }
-            mf_put4(hit, q, h);
-        }
-#pragma unroll 1
-        for (int q = 0; q < 4; ++q) {  // larger keys: the wave walks them one after another
-            const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q);
-            uint32_t h = mf_sel4(hit, q);
-            unsigned long long m = __ballot(c > kMatchLaneWalk);
-            while (m) {
-                const int src = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                const uint32_t sr = __shfl(r, src, 64), sc = __shfl(c, src, 64);
-                const uint32_t prow = (uint32_t)(wrow0 + (int64_t)src * 4 + q);
-                uint32_t tot = 0;
-                for (uint32_t j0 = 0; j0 < sc; j0 += 64) {  // sc <= the build's rows < 2^32 - 64
-                    const uint32_t j = j0 + (uint32_t)lane;
-                    bool pass = false;
-                    if (j < sc)
-                        pass = mf_candidate<BYTES, MODE>(tv, pr, dup_ref_row(tv.dup_rows, sr, tv.off_mask, j), prow,
-                                                         flags, nflags, flags_only);
-                    const unsigned long long b = __ballot(pass);
-                    tot += (uint32_t)__popcll(b);
-                    if (MODE == kMfExists && b != 0) break;  // wave-uniform
-                }
-                if (lane == src) h = tot;
-            }
-            mf_put4(hit, q, h);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            matched += hit[q] != 0;
-            pairs += hit[q];
-        }
-        if (out_bitmap != nullptr) {
-            unsigned long long b[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) b[q] = __ballot(hit[q] != 0);
-            if (lane < 4) {  // lane w assembles word w of the wave's four
-                unsigned long long word = 0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) word |= spread16_by4(b[q] >> (16 * lane)) << q;
-                const int64_t widx = (wrow0 >> 6) + lane;
-                if (widx < nwords) out_bitmap[widx] = word;  // rows >= n have no candidate: tail bits 0
-            }
-        }
-        if constexpr (MODE == kMfFull) {
-            if (out_counts != nullptr) {
-                if (cvec && row0 + 4 <= n) {
-                    *reinterpret_cast<uint4*>(out_counts + row0) = make_uint4(hit[0], hit[1], hit[2], hit[3]);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (row0 + q < n) out_counts[row0 + q] = hit[q];
-                }
-            }
-        }
-    }
-    // statistics: wave reduction, then one atomic per workgroup and statistic
-    const unsigned long long wm = wave_sum<unsigned long long>(matched);
-    const unsigned long long wc = wave_sum<unsigned long long>(cand);
-    unsigned long long wp = 0;
-    if constexpr (MODE == kMfFull) wp = wave_sum<unsigned long long>(pairs);
-    if (lane == 0) { s_m[wave] = wm; s_p[wave] = wp; s_c[wave] = wc; }
-    __syncthreads();
-    if (threadIdx.x == 0 && stats != nullptr) {
-        unsigned long long tm = 0, tp = 0, tc = 0;
-        for (int w = 0; w < kMatchThreads / 64; ++w) { tm += s_m[w]; tp += s_p[w]; tc += s_c[w]; }
-        if (tm && (stat_mask & 1)) atomicAdd(stats, tm);
-        if (tp && (stat_mask & 2)) atomicAdd(stats + 1, tp);
-        if (tc) atomicAdd(stats + 2, tc);
-    }
-}
-
-hipError_t launch_probe_match_filtered(int key_bytes, const TableView& tv, const PairPred& pr, const void* keys,
-                                       const uint8_t* valid, int64_t voff, int64_t n, uint8_t* out_bitmap,
-                                       uint32_t* out_counts, uint8_t* flags, int64_t nflags, int64_t* d_stats,
-                                       hipStream_t s) {
-    unsigned long long* stats = reinterpret_cast<unsigned long long*>(d_stats);
-    const int stat_mask = ((out_bitmap != nullptr || out_counts != nullptr) ? 1 : 0) | (out_counts != nullptr ? 2 : 0);
-    if (stats != nullptr) {
-        hipError_t e = hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), s);
-        // the statistics nobody asked the walk for read -1: [1], or [0] and [1]
-        if (e == hipSuccess && stat_mask != 3)
-            e = hipMemsetAsync(stats + (stat_mask & 1), 0xFF, (size_t)(2 - (stat_mask & 1)) * 8, s);
-        if (e != hipSuccess) return e;
-    }
-    if (n <= 0) return hipSuccess;
-    const bool mark = flags != nullptr && nflags > 0;
-    const bool full = out_counts != nullptr || mark;
-    const bool flags_only = mark && out_bitmap == nullptr && out_counts == nullptr;
-    bool bytes = false;  // the BYTES compare loop only where a term needs it
-    for (int t = 0; t < pr.nterms; ++t) bytes = bytes || pr.t[t].cls == kPfBytes;
-    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15) == 0;
-    const bool cvec = (reinterpret_cast<uintptr_t>(out_counts) & 15) == 0;
-    const unsigned grid = (unsigned)std::min<int64_t>((n + kMatchRows - 1) / kMatchRows, kMatchMaxBlocks);
-    unsigned long long* bm = reinterpret_cast<unsigned long long*>(out_bitmap);
-#define DFP_MF(KT, HV, BY, MD)                                                                                    \
-    probe_match_filtered_kernel<KT, HV, BY, MD><<<grid, kMatchThreads, 0, s>>>(                                   \
-        tv, pr, keys, valid, voff, n, vec, bm, out_counts, cvec, mark ? flags : nullptr, mark ? (uint64_t)nflags : 0, \
-        flags_only, stats, stat_mask)
-#define DFP_MF_K(KT, HV)                                    \
-    do {                                                    \
-        if (bytes && full) DFP_MF(KT, HV, true, kMfFull);   \
-        else if (bytes) DFP_MF(KT, HV, true, kMfExists);    \
-        else if (full) DFP_MF(KT, HV, false, kMfFull);      \
-        else DFP_MF(KT, HV, false, kMfExists);              \
-    } while (0)
-    if (key_bytes == 8) {
-        if (valid) DFP_MF_K(int64_t, true); else DFP_MF_K(int64_t, false);
-    } else {
-        if (valid) DFP_MF_K(int32_t, true); else DFP_MF_K(int32_t, false);
-    }
-#undef DFP_MF_K
-#undef DFP_MF
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// filtered pair plan: the pair plan under a pair predicate, whose windows hold F, the pairs
-// of the probe that pass it, not S. What lookup_inner_join_probe_batch (inner.rs:79-129)
-// keeps of get_matching_indices (src/shared/shared.rs:29-47) once
-// apply_join_filter_to_indices (src/shared/datafusion_private.rs:295-328) has dropped the
-// failing pairs - the filter before any marking, as in full.rs:140-175 - without S ever
-// reaching memory. Count -> scan -> write, every pass a launch of its own: no workgroup
-// waits for another.
-//
-//   count  pair_plan_filtered_count_kernel  probe_match_filtered_kernel's full walk (no
-//          first-pass exit, no flag skip: the counts are exact). Keeps every row's ref and
-//          F-count and, per block of kPlanBlockRows rows, (rows with a pair in F, its pairs
-//          in F); bitmap and flags as the filtered match probe writes them; |S| by one
-//          atomic per workgroup into the plan's header.
-//   scan   pair_plan_filtered_scan_kernel   one workgroup: exclusive scan of the block
-//          totals in place, the grand totals behind the last block, the header and d_stats.
-//   emit   pair_window_filtered_kernel      the same grid of blocks. A block whose scanned
-//          range misses the window leaves after two loads. Otherwise its rows' F-counts
-//          are scanned (64-bit ranks) and every row whose passing pairs meet the window
-//          walks its candidates again, in the count's order: pair k of the row goes to rank
-//          offset + k. Rows without a pair in F are never walked again.
-// ---------------------------------------------------------------------------
-FilteredPlanLayout pair_plan_filtered_layout(int64_t n) {
-    FilteredPlanLayout L;
-    L.nblocks = (n + kPlanBlockRows - 1) / kPlanBlockRows;
-    L.refs = kPlanHeaderBytes;
-    L.counts = L.refs + ((4 * n + 15) & ~(int64_t)15);
-    L.blocks = L.counts + ((4 * n + 15) & ~(int64_t)15);
-    L.bytes = L.blocks + 16 * (L.nblocks + 1);
-    return L;
-}
-
-template <typename K, bool HAS_VALID, bool BYTES>
-__global__ void __launch_bounds__(kMatchThreads)
-pair_plan_filtered_count_kernel(TableView tv, PairPred pr, const void* __restrict__ keys,
-                                const uint8_t* __restrict__ valid, int64_t voff, int64_t n, bool vec,
-                                unsigned long long* __restrict__ out_bitmap, uint8_t* flags, uint64_t nflags,
-                                uint32_t* __restrict__ refs, uint32_t* __restrict__ counts, bool svec,
-                                unsigned long long* __restrict__ btot, unsigned long long* __restrict__ cand_total) {
-    __shared__ unsigned long long s_m[kMatchThreads / 64], s_p[kMatchThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t nwords = (n + 63) >> 6;
-    unsigned long long cand = 0;
-    for (int64_t blk = blockIdx.x; blk * kMatchRows < n; blk += gridDim.x) {
-        const int64_t wrow0 = blk * kMatchRows + (int64_t)wave * 256;
-        const int64_t row0 = wrow0 + (int64_t)lane * 4;
-        unsigned long long matched = 0, pairs = 0;
-        if (wrow0 < n) {  // the whole wave (a wave past n only joins the block's totals)
-            uint32_t ref[4] = {kMiss, kMiss, kMiss, kMiss}, cnt[4] = {0, 0, 0, 0};
-            if (row0 < n) lookup4<K, HAS_VALID>(tv, keys, valid, voff, n, vec, row0, ref, cnt);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                cnt[q] = resolve_count(tv.dup_rows, ref[q], cnt[q], tv.off_mask);
-                cand += cnt[q];
-            }
-            uint32_t hit[4] = {0, 0, 0, 0};  // hit[q]: the row's pairs in F
-#pragma unroll 1
-            for (int q = 0; q < 4; ++q) {  // keys the owning lane walks
-                const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q);
-                uint32_t h = 0;
-                if (c != 0 && c <= kMatchLaneWalk) {  // a matched row: row0 + q < n
-                    const uint32_t prow = (uint32_t)(row0 + q);
-                    for (uint32_t j = 0; j < c; ++j) {
-                        const uint32_t row = (r & kDupFlag) ? dup_ref_row(tv.dup_rows, r, tv.off_mask, j) : r;
-                        h += mf_candidate<BYTES, kMfFull>(tv, pr, row, prow, flags, nflags, false);
-                    }
-                }
-                mf_put4(hit, q, h);
-            }
-#pragma unroll 1
-            for (int q = 0; q < 4; ++q) {  // larger keys: the wave walks them one after another
-                const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q);
-                uint32_t h = mf_sel4(hit, q);
-                unsigned long long m = __ballot(c > kMatchLaneWalk);
-                while (m) {
-                    const int src = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    const uint32_t sr = __shfl(r, src, 64), sc = __shfl(c, src, 64);
-                    const uint32_t prow = (uint32_t)(wrow0 + (int64_t)src * 4 + q);
-                    uint32_t tot = 0;
-                    for (uint32_t j0 = 0; j0 < sc; j0 += 64) {  // sc <= the build's rows < 2^32 - 64
-                        const uint32_t j = j0 + (uint32_t)lane;
-                        bool pass = false;
-                        if (j < sc)
-                            pass = mf_candidate<BYTES, kMfFull>(tv, pr, dup_ref_row(tv.dup_rows, sr, tv.off_mask, j),
-                                                                prow, flags, nflags, false);
-                        tot += (uint32_t)__popcll(__ballot(pass));
-                    }
-                    if (lane == src) h = tot;
-                }
-                mf_put4(hit, q, h);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                matched += hit[q] != 0;
-                pairs += hit[q];
-            }
-            if (out_bitmap != nullptr) {
-                unsigned long long b[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) b[q] = __ballot(hit[q] != 0);
-                if (lane < 4) {  // lane w assembles word w of the wave's four
-                    unsigned long long word = 0;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) word |= spread16_by4(b[q] >> (16 * lane)) << q;
-                    const int64_t widx = (wrow0 >> 6) + lane;
-                    if (widx < nwords) out_bitmap[widx] = word;  // rows >= n have no candidate: tail bits 0
-                }
-            }
-            if (svec && row0 + 4 <= n) {
-                *reinterpret_cast<uint4*>(refs + row0) = make_uint4(ref[0], ref[1], ref[2], ref[3]);
-                *reinterpret_cast<uint4*>(counts + row0) = make_uint4(hit[0], hit[1], hit[2], hit[3]);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (row0 + q < n) {
-                        refs[row0 + q] = ref[q];
-                        counts[row0 + q] = hit[q];
-                    }
-            }
-        }
-        const unsigned long long wm = wave_sum<unsigned long long>(matched);
-        const unsigned long long wp = wave_sum<unsigned long long>(pairs);
-        if (lane == 0) { s_m[wave] = wm; s_p[wave] = wp; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long tm = 0, tp = 0;
-            for (int w = 0; w < kMatchThreads / 64; ++w) { tm += s_m[w]; tp += s_p[w]; }
-            btot[2 * blk] = tm;
-            btot[2 * blk + 1] = tp;
-        }
-        __syncthreads();
-    }
-    // |S|: wave reduction, then one atomic per workgroup
-    const unsigned long long wc = wave_sum<unsigned long long>(cand);
-    if (lane == 0) s_m[wave] = wc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long tc = 0;
-        for (int w = 0; w < kMatchThreads / 64; ++w) tc += s_m[w];
-        if (tc) atomicAdd(cand_total, tc);
-    }
-}
-
-constexpr int kFpScanThreads = 1024;
-constexpr int kFpScanPer = 8;  // block totals per thread and round
-
-// header: [0] rows with a pair in F, [1] |F|, [2] |S| (zeroed before the count, which adds to
-// it); btot[2 * nblocks], btot[2 * nblocks + 1]: the same totals, so that block b's range of
-// ranks is [btot[2b + 1], btot[2b + 3]) for every b
-__global__ void __launch_bounds__(kFpScanThreads)
-pair_plan_filtered_scan_kernel(unsigned long long* __restrict__ btot, int64_t nblocks,
-                               unsigned long long* __restrict__ header, long long* __restrict__ d_stats) {
-    __shared__ unsigned long long s_w[kFpScanThreads / 64];
-    unsigned long long run_m = 0, run_p = 0;
-    for (int64_t base = 0; base < nblocks; base += (int64_t)kFpScanThreads * kFpScanPer) {
-        const int64_t i0 = base + (int64_t)threadIdx.x * kFpScanPer;
-        unsigned long long vm[kFpScanPer], vp[kFpScanPer], sm = 0, sp = 0;
-#pragma unroll
-        for (int q = 0; q < kFpScanPer; ++q) {
-            const bool in = i0 + q < nblocks;
-            vm[q] = in ? btot[2 * (i0 + q)] : 0ull;
-            vp[q] = in ? btot[2 * (i0 + q) + 1] : 0ull;
-            sm += vm[q];
-            sp += vp[q];
-        }
-        unsigned long long tm, tp;
-        unsigned long long em = run_m + block_excl_scan<unsigned long long>(sm, s_w, &tm);
-        unsigned long long ep = run_p + block_excl_scan<unsigned long long>(sp, s_w, &tp);
-#pragma unroll
-        for (int q = 0; q < kFpScanPer; ++q) {
-            if (i0 + q < nblocks) {
-                btot[2 * (i0 + q)] = em;
-                btot[2 * (i0 + q) + 1] = ep;
-            }
-            em += vm[q];
-            ep += vp[q];
-        }
-        run_m += tm;
-        run_p += tp;
-    }
-    if (threadIdx.x == 0) {
-        btot[2 * nblocks] = run_m;
-        btot[2 * nblocks + 1] = run_p;
-        header[0] = run_m;
-        header[1] = run_p;
-        if (d_stats != nullptr) {
-            d_stats[0] = (long long)run_m;
-            d_stats[1] = (long long)run_p;
-            d_stats[2] = (long long)header[2];
-        }
-    }
-}
-
-hipError_t launch_pair_plan_filtered(int key_bytes, const TableView& tv, const PairPred& pr, const void* keys,
-                                     const uint8_t* valid, int64_t voff, int64_t n, void* plan, uint8_t* out_bitmap,
-                                     uint8_t* flags, int64_t nflags, int64_t* d_stats, hipStream_t s) {
-    const FilteredPlanLayout L = pair_plan_filtered_layout(n);
-    char* p = static_cast<char*>(plan);
-    unsigned long long* header = reinterpret_cast<unsigned long long*>(p);
-    uint32_t* refs = reinterpret_cast<uint32_t*>(p + L.refs);
-    uint32_t* counts = reinterpret_cast<uint32_t*>(p + L.counts);
-    unsigned long long* btot = reinterpret_cast<unsigned long long*>(p + L.blocks);
-    hipError_t e = hipMemsetAsync(header, 0, kPlanHeaderBytes, s);
-    if (e != hipSuccess) return e;
-    if (n > 0) {
-        const bool mark = flags != nullptr && nflags > 0;
-        bool bytes = false;  // the BYTES compare loop only where a term needs it
-        for (int t = 0; t < pr.nterms; ++t) bytes = bytes || pr.t[t].cls == kPfBytes;
-        const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15) == 0;
-        const bool svec = (reinterpret_cast<uintptr_t>(plan) & 15) == 0;
-        const unsigned grid = (unsigned)std::min<int64_t>(L.nblocks, kMatchMaxBlocks);
-        unsigned long long* bm = reinterpret_cast<unsigned long long*>(out_bitmap);
-#define DFP_FPC(KT, HV, BY)                                                                                          \
-    pair_plan_filtered_count_kernel<KT, HV, BY><<<grid, kMatchThreads, 0, s>>>(                                      \
-        tv, pr, keys, valid, voff, n, vec, bm, mark ? flags : nullptr, mark ? (uint64_t)nflags : 0, refs, counts, svec, \
-        btot, header + 2)
-#define DFP_FPC_K(KT, HV)                        \
-    do {                                         \
-        if (bytes) DFP_FPC(KT, HV, true);        \
-        else DFP_FPC(KT, HV, false);             \
-    } while (0)
-        if (key_bytes == 8) {
-            if (valid) DFP_FPC_K(int64_t, true); else DFP_FPC_K(int64_t, false);
-        } else {
-            if (valid) DFP_FPC_K(int32_t, true); else DFP_FPC_K(int32_t, false);
-        }
-#undef DFP_FPC_K
-#undef DFP_FPC
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    pair_plan_filtered_scan_kernel<<<1, kFpScanThreads, 0, s>>>(btot, L.nblocks, header,
-                                                                reinterpret_cast<long long*>(d_stats));
-    return hipGetLastError();
-}
-
-// Inclusive wave64 scan of a u64 < 2^40 in two DPP scans: the low 24 bits (64 lanes: < 2^30)
-// and the bits above them (< 2^16 each: < 2^22). A lane's four F-counts are below 2^34.
-__device__ __forceinline__ unsigned long long wave_incl_scan40_dpp(unsigned long long v) {
-    const uint32_t lo = wave_incl_scan_dpp((uint32_t)v & 0xFFFFFFu);
-    const uint32_t hi = wave_incl_scan_dpp((uint32_t)(v >> 24));
-    return ((unsigned long long)hi << 24) + lo;
-}
-
-template <bool BYTES, bool HAS_PROBE_IDS>
-__global__ void __launch_bounds__(kMatchThreads)
-pair_window_filtered_kernel(TableView tv, PairPred pr, const uint32_t* __restrict__ refs,
-                            const uint32_t* __restrict__ counts, bool svec, int64_t n, int64_t nblocks,
-                            const unsigned long long* __restrict__ btot, const uint32_t* __restrict__ probe_ids,
-                            uint32_t pbase, unsigned long long pair_lo, unsigned long long cap,
-                            uint64_t* __restrict__ out_b, uint32_t* __restrict__ out_p,
-                            long long* __restrict__ d_written) {
-    __shared__ unsigned long long s_w[kMatchThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && d_written != nullptr) {
-        const unsigned long long total = btot[2 * nblocks + 1];
-        const unsigned long long w = pair_lo < total ? total - pair_lo : 0ull;
-        *d_written = (long long)(w < cap ? w : cap);
-    }
-    if ((int64_t)blockIdx.x >= nblocks || cap == 0) return;
-    // the block's ranks [base, next) against the window [pair_lo, hi); every rank is below
-    // |F|, so the window's end needs no clamp (pair_lo < 2^63, cap <= 2^42: no overflow)
-    const unsigned long long base = btot[2 * (int64_t)blockIdx.x + 1], next = btot[2 * (int64_t)blockIdx.x + 3];
-    const unsigned long long hi = pair_lo + cap;
-    if (next <= pair_lo || base >= hi) return;  // the whole workgroup
-    const int64_t wrow0 = (int64_t)blockIdx.x * kPlanBlockRows + (int64_t)wave * 256;
-    const int64_t row0 = wrow0 + (int64_t)lane * 4;
-    uint32_t ref[4] = {kMiss, kMiss, kMiss, kMiss}, fc[4] = {0, 0, 0, 0};
-    if (svec && row0 + 4 <= n) {
-        const uint4 r = *reinterpret_cast<const uint4*>(refs + row0);
-        const uint4 c = *reinterpret_cast<const uint4*>(counts + row0);
-        ref[0] = r.x; ref[1] = r.y; ref[2] = r.z; ref[3] = r.w;
-        fc[0] = c.x; fc[1] = c.y; fc[2] = c.z; fc[3] = c.w;
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (row0 + q < n) {
-                ref[q] = refs[row0 + q];
-                fc[q] = counts[row0 + q];
-            }
-    }
-    // 64-bit exclusive prefix of the F-counts inside the block
-    const unsigned long long mine = (unsigned long long)fc[0] + fc[1] + fc[2] + fc[3];
-    const unsigned long long incl = wave_incl_scan40_dpp(mine);
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    unsigned long long off = base + (incl - mine);
-    for (int w = 0; w < wave; ++w) off += s_w[w];
-    // off4[q]: rank of the row's first passing pair; cnt[q]: its candidates if any of its
-    // passing pairs is in the window, else 0 (the row is not walked).
-    // The candidate count is not kept in the plan: ref_count(ref) here must equal the count
-    // pass's resolve_count(lookup4's count), because the lane / wave split below and the walk's
-    // order follow it. It does for every layout - a single row 1, a packed or run count from the
-    // ref's bits, else dup_rows[offset], which is also what lookup4's inline bucket count and
-    // the side bucket's row count of key 0 stand for. A layout whose lookup count is not
-    // recoverable from the ref has to store the count in the plan (as pair_plan_lookup_kernel does).
-    unsigned long long off4[4];
-    uint32_t cnt[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        off4[q] = off;
-        off += fc[q];
-        const bool in = fc[q] != 0 && off > pair_lo && off4[q] < hi;
-        cnt[q] = in ? ref_count(tv.dup_rows, ref[q], tv.off_mask) : 0u;
-    }
-#pragma unroll 1
-    for (int q = 0; q < 4; ++q) {  // keys the owning lane walks: adjacent lanes' rows are adjacent ranks
-        const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q), f = mf_sel4(fc, q);
-        if (c != 0 && c <= kMatchLaneWalk) {
-            const unsigned long long o = q == 0 ? off4[0] : (q == 1 ? off4[1] : (q == 2 ? off4[2] : off4[3]));
-            const uint32_t prow = (uint32_t)(row0 + q);
-            const uint32_t pid = HAS_PROBE_IDS ? probe_ids[prow] : prow + pbase;
-            uint32_t k = 0;
-            for (uint32_t j = 0; j < c && k < f && o + k < hi; ++j) {
-                const uint32_t row = (r & kDupFlag) ? dup_ref_row(tv.dup_rows, r, tv.off_mask, j) : r;
-                const uint64_t id = tv.row_ids != nullptr ? tv.row_ids[row] : (uint64_t)row;
-                if (pf_pair_passes<BYTES>(pr, true, id, prow)) {
-                    const unsigned long long rank = o + k;
-                    if (rank >= pair_lo) {  // rank < hi: the loop's condition
-                        out_b[rank - pair_lo] = id;
-                        out_p[rank - pair_lo] = pid;
-                    }
-                    ++k;
-                }
-            }
-        }
-    }
-#pragma unroll 1
-    for (int q = 0; q < 4; ++q) {  // larger keys: the wave walks them, a round's stores are contiguous
-        const uint32_t r = mf_sel4(ref, q), c = mf_sel4(cnt, q), f = mf_sel4(fc, q);
-        const unsigned long long o = q == 0 ? off4[0] : (q == 1 ? off4[1] : (q == 2 ? off4[2] : off4[3]));
-        unsigned long long m = __ballot(c > kMatchLaneWalk);
-        while (m) {
-            const int src = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const uint32_t sr = __shfl(r, src, 64), sc = __shfl(c, src, 64), sf = __shfl(f, src, 64);
-            const unsigned long long so = __shfl(o, src, 64);
-            const uint32_t prow = (uint32_t)(wrow0 + (int64_t)src * 4 + q);
-            const uint32_t pid = HAS_PROBE_IDS ? probe_ids[prow] : prow + pbase;
-            uint32_t tot = 0;  // the row's passing pairs before this round
-            for (uint32_t j0 = 0; j0 < sc && tot < sf && so + tot < hi; j0 += 64) {  // wave-uniform
-                const uint32_t j = j0 + (uint32_t)lane;
-                bool pass = false;
-                uint64_t id = 0;
-                if (j < sc) {
-                    const uint32_t row = dup_ref_row(tv.dup_rows, sr, tv.off_mask, j);
-                    id = tv.row_ids != nullptr ? tv.row_ids[row] : (uint64_t)row;
-                    pass = pf_pair_passes<BYTES>(pr, true, id, prow);
-                }
-                const unsigned long long b = __ballot(pass);
-                const uint32_t k = tot + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-                const unsigned long long rank = so + k;
-                if (pass && k < sf && rank >= pair_lo && rank < hi) {
-                    out_b[rank - pair_lo] = id;
-                    out_p[rank - pair_lo] = pid;
-                }
-                tot += (uint32_t)__popcll(b);
-            }
-        }
-    }
-}
-
-hipError_t launch_pair_window_filtered(const TableView& tv, const PairPred& pr, const void* plan, int64_t n,
-                                       const uint32_t* probe_ids, uint32_t probe_base, int64_t pair_lo,
-                                       int64_t capacity, uint64_t* out_b, uint32_t* out_p, int64_t* d_written,
-                                       hipStream_t s) {
-    const FilteredPlanLayout L = pair_plan_filtered_layout(n);
-    const char* p = static_cast<const char*>(plan);
-    const uint32_t* refs = reinterpret_cast<const uint32_t*>(p + L.refs);
-    const uint32_t* counts = reinterpret_cast<const uint32_t*>(p + L.counts);
-    const unsigned long long* btot = reinterpret_cast<const unsigned long long*>(p + L.blocks);
-    bool bytes = false;
-    for (int t = 0; t < pr.nterms; ++t) bytes = bytes || pr.t[t].cls == kPfBytes;
-    const bool svec = (reinterpret_cast<uintptr_t>(plan) & 15) == 0;
-    const unsigned grid = (unsigned)std::max<int64_t>(L.nblocks, 1);  // block 0 writes *d_written
-#define DFP_FPW(BY, PI)                                                                                         \
-    pair_window_filtered_kernel<BY, PI><<<grid, kMatchThreads, 0, s>>>(                                         \
-        tv, pr, refs, counts, svec, n, L.nblocks, btot, probe_ids, probe_base, (unsigned long long)pair_lo,      \
-        (unsigned long long)capacity, out_b, out_p, reinterpret_cast<long long*>(d_written))
-    if (bytes) {
-        if (probe_ids != nullptr) DFP_FPW(true, true); else DFP_FPW(true, false);
-    } else {
-        if (probe_ids != nullptr) DFP_FPW(false, true); else DFP_FPW(false, false);
-    }
-#undef DFP_FPW
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// pair plan, pass 1: the match probe's lookup, kept per row. Every row's ref and resolved
-// pair count go to the plan's scratch, and every block of kPlanBlockRows rows leaves its
-// (matched rows, pairs) totals; the scan of those totals and the compaction are launches
-// of their own (hj_window.hip), so no workgroup waits for another. Where the reference's
-// get_matching_indices (src/shared/shared.rs:29-47) emits a probe batch's pairs in one
-// piece, the plan keeps "how many pairs, and where" and the windows emit them in slices.
-// ---------------------------------------------------------------------------
-static_assert(kPlanBlockRows == kMatchRows, "a plan block is one iteration of the match probe's workgroup");
-
-template <typename K, bool HAS_VALID>
-__global__ void __launch_bounds__(kMatchThreads)
-pair_plan_lookup_kernel(TableView tv, const void* __restrict__ keys, const uint8_t* __restrict__ valid, int64_t voff,
-                        int64_t n, bool vec, uint32_t* __restrict__ refs, uint32_t* __restrict__ counts, bool svec,
-                        unsigned long long* __restrict__ btot) {
-    __shared__ unsigned long long s_m[kMatchThreads / 64], s_p[kMatchThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t blk = blockIdx.x; blk * kMatchRows < n; blk += gridDim.x) {
-        const int64_t row0 = blk * kMatchRows + (int64_t)threadIdx.x * 4;
-        uint32_t ref[4] = {kMiss, kMiss, kMiss, kMiss}, cnt[4] = {0, 0, 0, 0};
-        if (row0 < n) lookup4<K, HAS_VALID>(tv, keys, valid, voff, n, vec, row0, ref, cnt);
-        unsigned long long matched = 0, pairs = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            cnt[q] = resolve_count(tv.dup_rows, ref[q], cnt[q], tv.off_mask);
-            matched += cnt[q] != 0;
-            pairs += cnt[q];
-        }
-        if (svec && row0 + 4 <= n) {
-            *reinterpret_cast<uint4*>(refs + row0) = make_uint4(ref[0], ref[1], ref[2], ref[3]);
-            *reinterpret_cast<uint4*>(counts + row0) = make_uint4(cnt[0], cnt[1], cnt[2], cnt[3]);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (row0 + q < n) {
-                    refs[row0 + q] = ref[q];
-                    counts[row0 + q] = cnt[q];
-                }
-        }
-        const unsigned long long wm = wave_sum<unsigned long long>(matched);
-        const unsigned long long wp = wave_sum<unsigned long long>(pairs);
-        if (lane == 0) { s_m[wave] = wm; s_p[wave] = wp; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long tm = 0, tp = 0;
-            for (int w = 0; w < kMatchThreads / 64; ++w) { tm += s_m[w]; tp += s_p[w]; }
-            btot[2 * blk] = tm;
-            btot[2 * blk + 1] = tp;
-        }
-        __syncthreads();
-    }
-}
-
-hipError_t launch_pair_plan_lookup(int key_bytes, const TableView& tv, const void* keys, const uint8_t* valid,
-                                   int64_t voff, int64_t n, uint32_t* refs, uint32_t* counts,
-                                   unsigned long long* btot, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    const bool vec = (reinterpret_cast<uintptr_t>(keys) & 15) == 0;
-    const bool svec = ((reinterpret_cast<uintptr_t>(refs) | reinterpret_cast<uintptr_t>(counts)) & 15) == 0;
-    const unsigned grid = (unsigned)std::min<int64_t>((n + kMatchRows - 1) / kMatchRows, kMatchMaxBlocks);
-#define DFP_PLAN(KT, HV) \
-    pair_plan_lookup_kernel<KT, HV><<<grid, kMatchThreads, 0, s>>>(tv, keys, valid, voff, n, vec, refs, counts, svec, btot)
-    if (key_bytes == 8) {
-        if (valid) DFP_PLAN(int64_t, true); else DFP_PLAN(int64_t, false);
-    } else {
-        if (valid) DFP_PLAN(int32_t, true); else DFP_PLAN(int32_t, false);
-    }
-#undef DFP_PLAN
     return hipGetLastError();
 }
 

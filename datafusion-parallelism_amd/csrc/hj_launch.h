@@ -1,6 +1,6 @@
 // hj_launch.h — host-callable launchers of the gfx950 kernels (implemented in
-// hj_kernels.hip). Every launcher is asynchronous on `stream` and returns the
-// hipError_t of its launches.
+// hj_kernels.hip where a section names no other file). Every launcher is asynchronous on
+// `stream` and returns the hipError_t of its launches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "hj_device.h"
@@ -102,7 +102,7 @@ hipError_t launch_probe(int key_bytes, const TableView& tv, const void* keys, co
                         uint32_t* out_p, int64_t cap, int64_t* d_total, void* workspace,
                         hipEvent_t built, hipStream_t s);
 
-// ---- match probe -----------------------------------------------------------
+// ---- match probe (hj_match.hip) ----------------------------------------------
 // Per probe row whether (out_bitmap: ceil(n / 64) u64 words, every word written whole, bits
 // >= n zero) and how often (out_counts u32[n]) its key occurs; flags[id] = 1 for every build
 // row a pair of the probe would name (ids >= nflags skipped, nothing cleared); d_stats[0] =
@@ -117,7 +117,7 @@ hipError_t launch_probe_match(int key_bytes, const TableView& tv, const void* ke
                               int64_t n, uint8_t* out_bitmap, uint32_t* out_counts, uint8_t* flags, int64_t nflags,
                               int64_t* d_stats, void* workspace, uint64_t claim_bits, hipStream_t s);
 
-// ---- pair plan and pair window (hj_kernels.hip: the lookup; hj_window.hip: the rest) ----
+// ---- pair plan and pair window (hj_match.hip: the lookup; hj_window.hip: the rest) ----
 // The plan of a probe call's n rows, in caller memory of pair_plan_bytes(n) bytes (8-byte
 // aligned; every section starts at a multiple of 16 bytes from its base):
 //   header   u64 m = matched rows, u64 total = pairs (64 bytes reserved)
@@ -133,7 +133,7 @@ struct PlanLayout {
     int64_t nblocks;
 };
 PlanLayout pair_plan_layout(int64_t n);
-// pass 1 (hj_kernels.hip): refs[i], counts[i] of every row i < n, and per block of
+// pass 1 (hj_match.hip): refs[i], counts[i] of every row i < n, and per block of
 // kPlanBlockRows rows btot[2 * b] = matched rows, btot[2 * b + 1] = pairs. n > 0.
 hipError_t launch_pair_plan_lookup(int key_bytes, const TableView& tv, const void* keys, const uint8_t* valid,
                                    int64_t voff, int64_t n, uint32_t* refs, uint32_t* counts,
@@ -281,6 +281,8 @@ struct PairPred {
     int64_t build_rows, probe_rows;
     int nterms;
 };
+// whether a term compares BYTES: the kernels' BYTES = true instantiations, else BYTES = false
+bool pf_has_bytes(const PairPred& pr);
 // out_bitmap: ceil(n / 64) u64 words, bit i = pair i passes; *d_count = set bits
 hipError_t launch_pair_filter_test(const PairPred& pr, const uint64_t* bidx, const uint32_t* pidx, int64_t n,
                                    uint8_t* out_bitmap, int64_t* d_count, hipStream_t s);
@@ -296,7 +298,7 @@ hipError_t launch_compact_pairs(const uint64_t* bidx, const uint32_t* pidx, int6
                                 const unsigned long long* words, const unsigned long long* toff, uint64_t* out_b,
                                 uint32_t* out_p, hipStream_t s);
 
-// ---- filtered match probe (hj_kernels.hip: the match probe's lookup + the pair pass rule) ----
+// ---- filtered match probe (hj_match.hip: the match probe's lookup + the pair pass rule) ----
 // The match probe's outputs with F, the pairs of the probe that pass `pr`, in place of all its
 // pairs: out_bitmap / out_counts / flags as launch_probe_match defines them (every one
 // optional). d_stats (optional) int64[3]: [0] rows with a pair in F if a bitmap or counts are
@@ -308,7 +310,7 @@ hipError_t launch_probe_match_filtered(int key_bytes, const TableView& tv, const
                                        uint32_t* out_counts, uint8_t* flags, int64_t nflags, int64_t* d_stats,
                                        hipStream_t s);
 
-// ---- filtered pair plan (hj_kernels.hip: count, scan and emit under a pair predicate) ----
+// ---- filtered pair plan (hj_match.hip: count, scan and emit under a pair predicate) ----
 // The plan of a probe call's n rows under `pr`, in caller memory of
 // pair_plan_filtered_layout(n).bytes bytes (8-byte aligned):
 //   header   u64 rows with a pair in F, u64 |F|, u64 |S| (kPlanHeaderBytes reserved)

@@ -90,7 +90,7 @@ hipError_t launch_compact_pairs(const uint64_t* bidx, const uint32_t* pidx, int6
     return hipGetLastError();
 }
 
-static bool pf_has_bytes(const PairPred& pr) {
+bool pf_has_bytes(const PairPred& pr) {
     for (int t = 0; t < pr.nterms; ++t)
         if (pr.t[t].cls == kPfBytes) return true;
     return false;

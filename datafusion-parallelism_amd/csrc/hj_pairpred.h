@@ -1,7 +1,7 @@
 // hj_pairpred.h — the device side of the pair pass rule (include/hj.h, "pair filter"): whether
 // one pair (build row, probe row) passes a PairPred. Shared by the kernels that evaluate a
 // predicate on pairs in memory (hj_pairfilter.hip) and on the candidates of a lookup
-// (hj_kernels.hip, the filtered match probe). The predicate travels as a kernel argument, so
+// (hj_match.hip, the filtered match probe and pair plan). The predicate travels as a kernel argument, so
 // every descriptor - class, width, op, column - is wave-uniform and the switches over them
 // are scalar branches; only the operand gathers and the BYTES compare loop are per lane.
 #pragma once

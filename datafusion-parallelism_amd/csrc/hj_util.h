@@ -85,4 +85,68 @@ __device__ __forceinline__ T block_excl_scan(T v, T* s_w, T* total) {
     return off + incl - v;
 }
 
+// A lane's four consecutive u32 a[row0 .. row0 + 3] of an array of n: one 16-byte access where
+// the array is 16-byte aligned (`vec`) and holds all four, else one access per element
+// below n. The load leaves v[q] as it is for row0 + q >= n.
+__device__ __forceinline__ void store4_u32(uint32_t* __restrict__ a, int64_t row0, int64_t n, bool vec,
+                                           const uint32_t (&v)[4]) {
+    if (vec && row0 + 4 <= n) {
+        *reinterpret_cast<uint4*>(a + row0) = make_uint4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (row0 + q < n) a[row0 + q] = v[q];
+    }
+}
+__device__ __forceinline__ void load4_u32(const uint32_t* __restrict__ a, int64_t row0, int64_t n, bool vec,
+                                          uint32_t (&v)[4]) {
+    if (vec && row0 + 4 <= n) {
+        const uint4 x = *reinterpret_cast<const uint4*>(a + row0);
+        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (row0 + q < n) v[q] = a[row0 + q];
+    }
+}
+
+// The pair plans' scan (hj_window.hip, hj_match.hip): one workgroup of kPlanScanThreads threads
+// replaces the nblocks (u64, u64) pairs of btot by their exclusive prefix sums, in place;
+// *tot0, *tot1 = the sums of all of them, in every thread. s_w: kPlanScanThreads / 64 words of LDS.
+constexpr int kPlanScanThreads = 1024;
+constexpr int kPlanScanPer = 8;  // pairs per thread and round
+__device__ __forceinline__ void scan_block_totals(unsigned long long* __restrict__ btot, int64_t nblocks,
+                                                  unsigned long long* s_w, unsigned long long* tot0,
+                                                  unsigned long long* tot1) {
+    unsigned long long run_m = 0, run_p = 0;
+    for (int64_t base = 0; base < nblocks; base += (int64_t)kPlanScanThreads * kPlanScanPer) {
+        const int64_t i0 = base + (int64_t)threadIdx.x * kPlanScanPer;
+        unsigned long long vm[kPlanScanPer], vp[kPlanScanPer], sm = 0, sp = 0;
+#pragma unroll
+        for (int q = 0; q < kPlanScanPer; ++q) {
+            const bool in = i0 + q < nblocks;
+            vm[q] = in ? btot[2 * (i0 + q)] : 0ull;
+            vp[q] = in ? btot[2 * (i0 + q) + 1] : 0ull;
+            sm += vm[q];
+            sp += vp[q];
+        }
+        unsigned long long tm, tp;
+        unsigned long long em = run_m + block_excl_scan<unsigned long long>(sm, s_w, &tm);
+        unsigned long long ep = run_p + block_excl_scan<unsigned long long>(sp, s_w, &tp);
+#pragma unroll
+        for (int q = 0; q < kPlanScanPer; ++q) {
+            if (i0 + q < nblocks) {
+                btot[2 * (i0 + q)] = em;
+                btot[2 * (i0 + q) + 1] = ep;
+            }
+            em += vm[q];
+            ep += vp[q];
+        }
+        run_m += tm;
+        run_p += tp;
+    }
+    *tot0 = run_m;
+    *tot1 = run_p;
+}
+
 }  // namespace dfp

@@ -4,7 +4,7 @@
 // pairs in one piece. Here the pairs of one probe call can be had in slices of the canonical
 // order: a plan says how many pairs every matched row has and where they start, a window
 // writes pairs [lo, lo + capacity) from it. The plan's first pass (the lookup) is
-// pair_plan_lookup_kernel in hj_kernels.hip; this file needs the table only for the
+// pair_plan_lookup_kernel in hj_match.hip; this file needs the table only for the
 // duplicate segments and the explicit ids (hj_device.h).
 //
 //   pass 2  pair_plan_scan_kernel     one workgroup: exclusive scan of the blocks' (matched,
@@ -50,40 +50,12 @@ PlanLayout pair_plan_layout(int64_t n) {
     return L;
 }
 
-constexpr int kScanThreads = 1024;
-constexpr int kScanPer = 8;  // block totals per thread and round
-
-__global__ void __launch_bounds__(kScanThreads)
+__global__ void __launch_bounds__(kPlanScanThreads)
 pair_plan_scan_kernel(unsigned long long* __restrict__ btot, int64_t nblocks, unsigned long long* __restrict__ header,
                       unsigned long long* __restrict__ offsets, long long* __restrict__ d_total) {
-    __shared__ unsigned long long s_w[kScanThreads / 64];
-    unsigned long long run_m = 0, run_p = 0;
-    for (int64_t base = 0; base < nblocks; base += (int64_t)kScanThreads * kScanPer) {
-        const int64_t i0 = base + (int64_t)threadIdx.x * kScanPer;
-        unsigned long long vm[kScanPer], vp[kScanPer], sm = 0, sp = 0;
-#pragma unroll
-        for (int q = 0; q < kScanPer; ++q) {
-            const bool in = i0 + q < nblocks;
-            vm[q] = in ? btot[2 * (i0 + q)] : 0ull;
-            vp[q] = in ? btot[2 * (i0 + q) + 1] : 0ull;
-            sm += vm[q];
-            sp += vp[q];
-        }
-        unsigned long long tm, tp;
-        unsigned long long em = run_m + block_excl_scan<unsigned long long>(sm, s_w, &tm);
-        unsigned long long ep = run_p + block_excl_scan<unsigned long long>(sp, s_w, &tp);
-#pragma unroll
-        for (int q = 0; q < kScanPer; ++q) {
-            if (i0 + q < nblocks) {
-                btot[2 * (i0 + q)] = em;
-                btot[2 * (i0 + q) + 1] = ep;
-            }
-            em += vm[q];
-            ep += vp[q];
-        }
-        run_m += tm;
-        run_p += tp;
-    }
+    __shared__ unsigned long long s_w[kPlanScanThreads / 64];
+    unsigned long long run_m, run_p;
+    scan_block_totals(btot, nblocks, s_w, &run_m, &run_p);
     if (threadIdx.x == 0) {
         header[0] = run_m;
         header[1] = run_p;
@@ -102,19 +74,8 @@ pair_plan_compact_kernel(const uint32_t* __restrict__ refs, const uint32_t* __re
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t row0 = (int64_t)blockIdx.x * kPlanBlockRows + (int64_t)threadIdx.x * 4;
     uint32_t ref[4] = {kMiss, kMiss, kMiss, kMiss}, cnt[4] = {0, 0, 0, 0};
-    if (svec && row0 + 4 <= n) {
-        const uint4 r = *reinterpret_cast<const uint4*>(refs + row0);
-        const uint4 c = *reinterpret_cast<const uint4*>(counts + row0);
-        ref[0] = r.x; ref[1] = r.y; ref[2] = r.z; ref[3] = r.w;
-        cnt[0] = c.x; cnt[1] = c.y; cnt[2] = c.z; cnt[3] = c.w;
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (row0 + q < n) {
-                ref[q] = refs[row0 + q];
-                cnt[q] = counts[row0 + q];
-            }
-    }
+    load4_u32(refs, row0, n, svec, ref);
+    load4_u32(counts, row0, n, svec, cnt);
     uint32_t mc = 0;
     unsigned long long pc = 0;
 #pragma unroll
@@ -146,7 +107,7 @@ hipError_t launch_pair_plan_finish(void* plan, int64_t n, int64_t* d_total, hipS
     unsigned long long* header = reinterpret_cast<unsigned long long*>(p);
     unsigned long long* offsets = reinterpret_cast<unsigned long long*>(p + L.offsets);
     unsigned long long* btot = reinterpret_cast<unsigned long long*>(p + L.blocks);
-    pair_plan_scan_kernel<<<1, kScanThreads, 0, s>>>(btot, L.nblocks, header, offsets, reinterpret_cast<long long*>(d_total));
+    pair_plan_scan_kernel<<<1, kPlanScanThreads, 0, s>>>(btot, L.nblocks, header, offsets, reinterpret_cast<long long*>(d_total));
     if (L.nblocks > 0) {
         const bool svec = (reinterpret_cast<uintptr_t>(plan) & 15) == 0;
         pair_plan_compact_kernel<<<(unsigned)L.nblocks, kCompactThreads, 0, s>>>(
